@@ -3,7 +3,10 @@
 (BASELINE.json config 2: SynthesisNetworkFull_v18, 512^2, N=8 per GPU, fp32, eval,
 random latents + style maps, noise_mode='const', argmax parsing path as test.py runs it).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/<name>.npy, at most 64 MB in all (dump_outputs());
+weights and inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 N > 1: one rank per GPU.  Started through torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS
 a rank; started plainly as `python bench.py --gpus N` it is the launcher: before importing torch or touching the GPU it
@@ -85,6 +88,33 @@ def run_net(net, inp):
 def init_weights(net):
     from training.synthetic import fill_module_
     return fill_module_(net, 'cfg2.')      # name-keyed N(0,1) weights, noise_strength 0.1
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6    # --dump-outputs: bytes on disk, .npy headers included
+NPY_HEADER_BYTES = 1024         # (np.save writes 128 for these shapes)
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: write the arrays the timed path returned in its last step as <out_dir>/<name>.npy (float64 stays float64, every
+    other dtype becomes float32), at most DUMP_BYTES_MAX bytes of files in all.  The smallest arrays are served first; one that does not fit its share of what
+    is left is written as a fixed sample: the flattened elements at the first k indices of a RandomState(0) permutation, in ascending
+    index order (NumPy's legacy stream is frozen, so equal shapes give equal indices and two builds compare element for element).
+    Returns, per array, its full shape and how many elements were written."""
+    import numpy as np
+    arrays = {name: (t.detach().double() if t.dtype == torch.float64 else t.detach().float()).cpu().numpy()
+              for name, t in outputs.items() if t is not None}
+    os.makedirs(out_dir, exist_ok=True)
+    left, info = DUMP_BYTES_MAX - NPY_HEADER_BYTES * len(arrays), {}
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        k = min(a.size, left // (len(order) - i) // a.itemsize)
+        if k < a.size:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).permutation(a.size)[:k])]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        info[name] = dict(shape=list(arrays[name].shape), dtype=str(a.dtype), elements_written=int(k), sampled=bool(k < arrays[name].size))
+    return info
 
 
 def cpu_baseline(max_seconds=40.0):
@@ -572,7 +602,14 @@ def main():
                          "'bf16_1024' = config 5 (StyleGAN2 stack at 1024^2 in bf16, N=4); 'selftest' = launcher / rank plumbing on CPU over gloo with a stub forward (no measurement)")
     ap.add_argument('--no-secondary', action='store_true', help='headline mode: skip the config 3 / config 5 child runs')
     ap.add_argument('--channel-max', type=int, default=1024, help="config 5: widest layer (SURVEY 8d: 'channels 1024 -> 32')")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='headline mode: write the outputs of the last timed step (img, finetune_img, pred_parsing of rank 0) as DIR/<name>.npy, '
+                         f'at most {DUMP_BYTES_MAX // 10 ** 6} MB in all (larger outputs as a fixed seeded sample)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.mode != 'synthesis':
+        ap.error('--dump-outputs is implemented for the headline mode (--mode synthesis) only')
 
     from training import launch
     if args.gpus > 1 and not launch.launched_as_rank():
@@ -648,6 +685,8 @@ def main():
                                          'noise_mode=const, argmax parsing, random-init weights', images_per_gpu_per_step=args.batch,
                                 global_batch=args.batch * world, parallelism=f'replicas x{world}'),
                     roofline=roofline)
+        if args.dump_outputs:                                  # `out` is the last timed step's result; nothing has run on the GPU since
+            line['dumped_outputs'] = dict(dir=args.dump_outputs, arrays=dump_outputs(dict(zip(('img', 'finetune_img', 'pred_parsing'), out)), args.dump_outputs))
         if world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline()
         if world == 1 and not args.no_secondary and under_profiler():

@@ -233,6 +233,8 @@ def get_plugin(module_name, sources=None, extra_hipcc_flags=(), build_only=False
 
     sources = _resolve_sources(module_name, sources)
     so_path = plugin_path(module_name)
+    if is_up_to_date(module_name, sources, extra_hipcc_flags):
+        return _load(module_name, so_path, build_only, abi_name)     # no lock: a built tree may be read-only to the user who runs it
     digest = _digest(sources, extra_hipcc_flags)
     os.makedirs(os.path.join(CSRC_DIR, 'build'), exist_ok=True)
     lock_path = os.path.join(CSRC_DIR, 'build', module_name + '.lock')
@@ -255,6 +257,10 @@ def get_plugin(module_name, sources=None, extra_hipcc_flags=(), build_only=False
                     _log('Done.')
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
+    return _load(module_name, so_path, build_only, abi_name)
+
+
+def _load(module_name, so_path, build_only, abi_name):
     if build_only:
         return so_path
     plugin = NativePlugin(module_name, so_path, abi_name)      # abi_name: dev variants of a plugin built under another name

@@ -309,3 +309,25 @@ def test_custom_ops_clean_is_per_plugin_and_spares_live_links(tmp_path, monkeypa
     finally:
         sleeper.kill()
         sleeper.wait()
+
+
+def test_custom_ops_loads_an_up_to_date_plugin_without_the_build_lock(monkeypatch):
+    """A built tree may be read-only to the user who runs it (build and run as different users): loading an up-to-date plugin
+    must neither open nor take csrc/build/<plugin>.lock -- only a build does."""
+    import builtins
+    from torch_utils import custom_ops
+    custom_ops.verbosity = 'none'
+    custom_ops.get_plugin('bias_act_plugin', build_only=True)        # built (a no-op after build())
+    assert custom_ops.is_up_to_date('bias_act_plugin')
+    real_open = builtins.open
+
+    def no_lock_open(path, *a, **k):
+        assert not str(path).endswith('.lock'), path
+        return real_open(path, *a, **k)
+
+    def no_flock(*_):
+        raise AssertionError('build lock taken for an up-to-date plugin')
+    monkeypatch.setattr(builtins, 'open', no_lock_open)
+    monkeypatch.setattr(custom_ops.fcntl, 'flock', no_flock)
+    monkeypatch.setattr(custom_ops, '_cached_plugins', {})
+    assert custom_ops.get_plugin('bias_act_plugin').lib is not None
