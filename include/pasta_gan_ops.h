@@ -2,7 +2,7 @@
  * pasta_gan_ops.h -- C ABI of the MI355X (gfx950) kernels behind PASTA-GAN++'s
  * generator-synthesis operator API.
  *
- * Four shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing):
+ * Five shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing):
  *   bias_act_plugin.so      pg_bias_act
  *   upfirdn2d_plugin.so     pg_upfirdn2d, pg_upfirdn2d_bias_act, pg_upfirdn2d_with_odd_samples
  *   conv2d_plugin.so        fp32: pg_conv2d_{packed_size,pack_weight,forward,splitk_plan,forward_splitk}, pg_conv2d_winograd_*,
@@ -10,6 +10,7 @@
  *                           16-bit: pg_conv2d16_{packed_size,pack_weight,pack_weight_grouped,forward,splitk_plan,forward_splitk,up2_fused,wgrad,wgrad_plan,wgrad_x3}, pg_adam_flat_{chunk,step},
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8
+ *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -587,6 +588,19 @@ typedef struct pg_compose_job {
 } pg_compose_job;
 int pg_patch_compose_ordered_u8(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, void* stream);
 int pg_patch_routing_abi_version(void);
+
+/* augment_plugin.so -- ADA discriminator augmentation (training/augment.py, AugmentPipe).  float32, dense NCHW, C <= 65535 / 4 per sample batch.
+ * pg_augment_warp: x [n, c, h, w] -> y [n, c, 2(h+6), 2(w+6)]: reflect-pad by `margins` (device int32 [mx0, my0, mx1, my1], each clamped to
+ *   [0, w-1] / [0, h-1]), 2x upsample with the 12 taps `f` (device, the normalised sym6 filter), bilinear sampling (align_corners=False, zeros outside)
+ *   through the per-sample matrices `g_inv` (device float32 [n, 3, 3], pixel_out -> pixel_in before padding).  The 2x downsample is a pg_upfirdn2d call.
+ * pg_augment_warp_adjoint: dx = transpose(warp)(dy); `workspace` = n * c * 2(3h-2) * 2(3w-2) floats (need not be initialised).  No atomics.
+ * pg_augment_color: per sample, mat = device float32 [n, C, C + 1]; mode 0: y[c] = sum_k mat[c][k] x[k] + mat[c][C]; mode 1 (transpose):
+ *   y[c] = sum_k mat[k][c] x[k]; mode 2 (linear part): y[c] = sum_k mat[c][k] x[k].  C in {1, 3} (PG_ERR_UNSUPPORTED otherwise); hw = h * w. */
+int pg_augment_warp(const float* x, float* y, const float* g_inv, const int* margins, const float* f, int n, int c, int h, int w, void* stream);
+int pg_augment_warp_adjoint(const float* dy, float* workspace, float* dx, const float* g_inv, const int* margins, const float* f,
+                            int n, int c, int h, int w, void* stream);
+int pg_augment_color(const float* x, float* y, const float* mat, int n, int c, int hw, int mode, void* stream);
+int pg_augment_abi_version(void);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,7 @@ class StyleGAN2Loss:
         if do_Dmain or do_Dr1:                                       # D on real images (+ lazy R1)
             real_tmp = real_img.detach().requires_grad_(do_Dr1)
             real_logits = self.run_D(real_tmp, pose, real_c)
+            self.report('Loss/signs/real', real_logits.detach().sign())   # ADA's statistic (loss_fullbody.py:256; D, not D_parsing)
             self._real_and_r1(real_logits, real_tmp, do_Dmain, do_Dr1, gain, 'D', lambda: before_backward(2))
 
         loss_DPgen = 0

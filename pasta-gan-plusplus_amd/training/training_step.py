@@ -10,7 +10,9 @@ last round finished segments of the bucket are already being summed over RCCL on
 -> nan_to_num -> Adam step.  A phase the loss declares statically empty (Greg: path-length regularisation is
 commented out in the reference, loss_fullbody.py:200-221) is skipped on every rank alike; any other phase issues the same
 collectives on every rank whatever gradients it produced (training/ddp.py), and one that produced no gradient anywhere
-takes no optimizer step -- what the reference's Adam does with all-None gradients.  Then the G_ema update (:642-650).  ADA / ticks / snapshots / metrics are outside the hot path and not restated.
+takes no optimizer step -- what the reference's Adam does with all-None gradients.  Then the G_ema update (:642-650).
+With an `augment_pipe` (training/augment.py) D's image input is augmented and, with an `ada_target`, the ADA heuristic adjusts its `p`
+every `ada_interval` iterations on the device (:437-446, 656-660).  Ticks / snapshots / metrics are outside the hot path and not restated.
 """
 
 import copy
@@ -31,13 +33,37 @@ class Phase:
 
 class TrainingStep:
     def __init__(self, G_parts, D, D_parsing, loss, lr=0.0005, betas=(0.0, 0.99), eps=1e-8, G_reg_interval=4, D_reg_interval=16,
-                 batch_size=32, ema_kimg=10, ema_rampup=None, G_ema_parts=None, graphs=False):
+                 batch_size=32, ema_kimg=10, ema_rampup=None, G_ema_parts=None, graphs=False, augment_pipe=None, augment_p=0, ada_target=None,
+                 ada_interval=4, ada_kimg=500):
         """`G_parts`: dict name -> module for G_mapping / G_synthesis / G_const_encoding / G_style_encoding.
         `graphs` (single process only): every phase -- zero the bucket, forward, backward(s), nan_to_num, Adam step -- is captured into
         one hipGraph the second time it is due and replayed from then on: the ~9 000 kernel launches of an iteration stop being
         issued one by one from Python.  Measured (round 3, config 4, one MI355X): 312 ms per iteration replayed vs 304 ms eager -- outside the
         profiler the eager step is already GPU-bound (the 23-29 % idle seen under rocprofv3 is the profiler's own host cost), so this is an
-        option for hosts slower than the GPU box, off by default."""
+        option for hosts slower than the GPU box, off by default.
+        `augment_pipe` (an AugmentPipe, or None = no augmentation): goes into the loss's `augment_pipe` slot with `p` = `augment_p`; with
+        `ada_target` the signs of D's real logits (the loss's 'Loss/signs/real' report) are summed on the device and every `ada_interval`
+        iterations p <- max(p + sign(mean - ada_target) * batch_size * ada_interval / (ada_kimg * 1000), 0) (training_loop_fullbody.py:656-660),
+        without a host read; over several processes the sum and count are all-reduced first.  Not with `graphs` (random draws are not captured)."""
+        if augment_pipe is not None and graphs:
+            raise ValueError('TrainingStep: augment_pipe cannot be combined with graphs=True (the augmentation draws are not captured)')
+        self.augment_pipe, self.ada_target, self.ada_interval, self.ada_kimg = augment_pipe, ada_target, int(ada_interval), ada_kimg
+        self.ada_stats = None            # device float64 [sum of signs, count] since the last adjustment
+        if augment_pipe is not None:
+            augment_pipe.requires_grad_(False)
+            with torch.no_grad():
+                augment_pipe.p.copy_(torch.as_tensor(augment_p))
+            loss.augment_pipe = augment_pipe
+            if ada_target is not None:
+                self.ada_stats = torch.zeros([2], dtype=torch.float64, device=augment_pipe.p.device)
+                report = loss.report
+
+                def collect(name, value):
+                    if name == 'Loss/signs/real':
+                        self.ada_stats[0] += value.detach().sum()
+                        self.ada_stats[1] += value.numel()
+                    report(name, value)
+                loss.report = collect
         self.G_parts, self.D, self.D_parsing, self.loss = G_parts, D, D_parsing, loss
         self.batch_size, self.ema_kimg, self.ema_rampup = batch_size, ema_kimg, ema_rampup
         self.G_ema_parts = G_ema_parts if G_ema_parts is not None else {k: copy.deepcopy(m).eval().requires_grad_(False) for k, m in G_parts.items()}
@@ -211,6 +237,20 @@ class TrainingStep:
         self._update_ema()
         self.cur_nimg += self.batch_size
         self.batch_idx += 1
+        if self.ada_stats is not None and self.batch_idx % self.ada_interval == 0:
+            self._adjust_p()
+
+    @torch.no_grad()
+    def _adjust_p(self):
+        stats = self.ada_stats
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.all_reduce(stats)                          # Collector._sync: sum and count over the ranks
+        mean = stats[0] / stats[1].clamp(min=1)
+        step = self.batch_size * self.ada_interval / (self.ada_kimg * 1000)
+        adjust = torch.where(stats[1] > 0, torch.sign(mean - self.ada_target) * step, torch.zeros_like(mean))
+        p = self.augment_pipe.p
+        p.copy_((p + adjust.to(p.dtype)).clamp(min=0))
+        stats.zero_()
 
     @torch.no_grad()
     def _update_ema(self):
