@@ -9,7 +9,7 @@
  *                           pg_conv2d_up2_{forward,splitk_plan,forward_splitk}, pg_conv1x1_small, pg_conv3x3_cin1, pg_conv2d_wgrad{_plan,}, pg_split3_bf16_cl;
  *                           16-bit: pg_conv2d16_{packed_size,pack_weight,pack_weight_grouped,forward,splitk_plan,forward_splitk,up2_fused,wgrad,wgrad_plan,wgrad_x3}, pg_adam_flat_{chunk,step},
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
- *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8
+ *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
  *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
@@ -563,6 +563,9 @@ int pg_conv1x1_small16(const void* x, const float* w, const float* styles, const
  * weights, taps outside the source read 0 (INTER_LINEAR, BORDER_CONSTANT 0).  `jobs_device` lives in device memory.
  * pg_patch_compose_u8: canvas[p] = erode8x8(mask[..., 0])[p] == 255 ? patch[p] : canvas[p] (and the same into canvas2 if given):
  * the paste step of the de-normalisation (dataset.py:2624-2633); patch / canvas are HxWx3, mask HxWxmask_channels.
+ * The `_k` forms take the erode window: ksize x ksize, anchored at (ksize/2, ksize/2) as cv2.erode's default anchor, pixels outside the image
+ * ignored; 1 <= ksize <= 16, anything else returns PG_ERR_INVALID_ARG.  8 is the upper try-on mode's window (dataset.py:2589), 5 the lower and
+ * full modes' (:1827, :3345).  The forms without `_k` are the `_k` forms with ksize = 8.
  */
 typedef struct {
     const unsigned char* src;
@@ -573,6 +576,8 @@ typedef struct {
 int pg_warp_perspective_u8(const pg_warp_job* jobs_device, int njobs, int max_dst_pixels, void* stream);
 int pg_patch_compose_u8(const unsigned char* patch, const unsigned char* mask, unsigned char* canvas, unsigned char* canvas2,
                         int h, int w, int mask_channels, void* stream);
+int pg_patch_compose_u8_k(const unsigned char* patch, const unsigned char* mask, unsigned char* canvas, unsigned char* canvas2,
+                          int h, int w, int mask_channels, int ksize, void* stream);
 /* Round 6 -- the whole paste sequence of `njobs` canvases in one launch (a batch's de-normalised garments: dataset.py:2620-2633 run per part and per sample
  * in the reference): job = one h x w x 3 canvas, its parts in paste order (patch, mask; later parts overwrite earlier ones), and optionally a second canvas that
  * receives only the parts with to_canvas2 != 0.  Every pixel of the canvases is written (0 where no part's eroded mask is set).  `jobs_device` lives in device memory. */
@@ -587,6 +592,7 @@ typedef struct pg_compose_job {
     int pad_;
 } pg_compose_job;
 int pg_patch_compose_ordered_u8(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, void* stream);
+int pg_patch_compose_ordered_u8_k(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, int ksize, void* stream);
 int pg_patch_routing_abi_version(void);
 
 /* augment_plugin.so -- ADA discriminator augmentation (training/augment.py, AugmentPipe).  float32, dense NCHW, C <= 65535 / 4 per sample batch.

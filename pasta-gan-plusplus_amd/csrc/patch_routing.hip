@@ -52,24 +52,32 @@ __global__ __launch_bounds__(256) void warp_perspective_u8_kernel(const pg_warp_
     }
 }
 
-// canvas[p] = (erode8x8(mask channel 0)[p] == 255) ? patch[p] : canvas[p]      (dataset.py:2624-2630)
-// erode: minimum over the 8x8 window anchored at (4, 4), pixels outside the image ignored -> "== 255" iff every in-range tap is 255
+// The erode of the paste step: cv2.erode(mask, ones(k, k)) with OpenCV's default anchor (k/2, k/2), pixels outside the image ignored
+// -> "== 255" iff every in-range tap of the window [y - k/2, y - k/2 + k) x [x - k/2, x - k/2 + k) is 255.  K > 0 fixes the window at compile
+// time (8: the upper mode's, dataset.py:2589; 5: the lower and full modes', :1827 / :3345); K = 0 reads it from `k` (1..16).
+template <int K>
+__device__ __forceinline__ bool eroded_white(const uint8_t* __restrict__ mask, int y, int x, int h, int w, int mc, int k) {
+    const int ks = K > 0 ? K : k, a = ks / 2;
+    for (int ky = 0; ky < ks; ky++) {
+        const int yy = y + ky - a;
+        if (yy < 0 || yy >= h) continue;
+        for (int kx = 0; kx < ks; kx++) {
+            const int xx = x + kx - a;
+            if (xx < 0 || xx >= w) continue;
+            if (mask[((int64_t)yy * w + xx) * mc] != 255) return false;
+        }
+    }
+    return true;
+}
+
+// canvas[p] = (erode_kxk(mask channel 0)[p] == 255) ? patch[p] : canvas[p]      (dataset.py:2624-2630)
+template <int K>
 __global__ __launch_bounds__(256) void patch_compose_u8_kernel(const uint8_t* __restrict__ patch, const uint8_t* __restrict__ mask, uint8_t* __restrict__ canvas,
-                                                               uint8_t* __restrict__ canvas2, int h, int w, int mc) {
+                                                               uint8_t* __restrict__ canvas2, int h, int w, int mc, int k) {
     const int npix = h * w;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
         const int y = i / w, x = i - y * w;
-        bool all = true;
-        for (int ky = 0; ky < 8 && all; ky++) {
-            const int yy = y + ky - 4;
-            if (yy < 0 || yy >= h) continue;
-            for (int kx = 0; kx < 8; kx++) {
-                const int xx = x + kx - 4;
-                if (xx < 0 || xx >= w) continue;
-                if (mask[((int64_t)yy * w + xx) * mc] != 255) { all = false; break; }
-            }
-        }
-        if (all) {
+        if (eroded_white<K>(mask, y, x, h, w, mc, k)) {
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 const uint8_t v = patch[(int64_t)i * 3 + c];
@@ -83,7 +91,8 @@ __global__ __launch_bounds__(256) void patch_compose_u8_kernel(const uint8_t* __
 // The whole paste sequence of one canvas in one pass (round 6): the reference pastes its parts one after the other, later parts overwriting earlier ones
 // (dataset.py:2620-2633), i.e. a pixel ends up with the patch of the LAST part whose eroded mask is set there, or 0.  One job = one canvas (+ the copy that
 // skips the sleeve parts); one thread = one pixel, walking the job's parts in order.  Every canvas pixel is written: the canvases need no zero fill.
-__global__ __launch_bounds__(256) void patch_compose_ordered_u8_kernel(const pg_compose_job* __restrict__ jobs, int h, int w, int mc) {
+template <int K>
+__global__ __launch_bounds__(256) void patch_compose_ordered_u8_kernel(const pg_compose_job* __restrict__ jobs, int h, int w, int mc, int k) {
     const pg_compose_job* jb = jobs + blockIdx.y;
     const int npix = h * w, nparts = jb->nparts;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
@@ -91,17 +100,8 @@ __global__ __launch_bounds__(256) void patch_compose_ordered_u8_kernel(const pg_
         int last = -1, last2 = -1;
         for (int p = 0; p < nparts; p++) {
             const uint8_t* mask = jb->mask[p];
-            bool all = mask[(int64_t)i * mc] == 255;          // (the window's own pixel first: most pixels lie outside a part)
-            for (int ky = 0; ky < 8 && all; ky++) {
-                const int yy = y + ky - 4;
-                if (yy < 0 || yy >= h) continue;
-                for (int kx = 0; kx < 8; kx++) {
-                    const int xx = x + kx - 4;
-                    if (xx < 0 || xx >= w) continue;
-                    if (mask[((int64_t)yy * w + xx) * mc] != 255) { all = false; break; }
-                }
-            }
-            if (all) {
+            // (the window's own pixel first: most pixels lie outside a part; it is always in the window, since 0 <= k/2 < k)
+            if (mask[(int64_t)i * mc] == 255 && eroded_white<K>(mask, y, x, h, w, mc, k)) {
                 last = p;
                 if (jb->to_canvas2[p]) last2 = p;
             }
@@ -118,14 +118,26 @@ __global__ __launch_bounds__(256) void patch_compose_ordered_u8_kernel(const pg_
 
 PG_EXPORT int pg_patch_routing_abi_version(void) { return PG_ABI_VERSION; }
 
-PG_EXPORT int pg_patch_compose_ordered_u8(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, void* stream) {
+PG_EXPORT int pg_patch_compose_ordered_u8_k(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, int ksize, void* stream) {
     if (!jobs_device || njobs <= 0 || h <= 0 || w <= 0 || mask_channels <= 0) return PG_ERR_INVALID_ARG;
+    if (ksize < 1 || ksize > 16) return PG_ERR_INVALID_ARG;
     if ((int64_t)h * w > 0x3fffffffLL) return PG_ERR_TOO_LARGE;
     if (njobs > 65535) return PG_ERR_TOO_LARGE;
     int bx = (h * w + 255) / 256;
     if (bx > 1024) bx = 1024;
-    hipLaunchKernelGGL(patch_compose_ordered_u8_kernel, dim3((unsigned)bx, (unsigned)njobs), dim3(256), 0, (hipStream_t)stream, jobs_device, h, w, mask_channels);
+    const dim3 grid((unsigned)bx, (unsigned)njobs);
+    const hipStream_t st = (hipStream_t)stream;
+    if (ksize == 8)
+        hipLaunchKernelGGL(patch_compose_ordered_u8_kernel<8>, grid, dim3(256), 0, st, jobs_device, h, w, mask_channels, 8);
+    else if (ksize == 5)
+        hipLaunchKernelGGL(patch_compose_ordered_u8_kernel<5>, grid, dim3(256), 0, st, jobs_device, h, w, mask_channels, 5);
+    else
+        hipLaunchKernelGGL(patch_compose_ordered_u8_kernel<0>, grid, dim3(256), 0, st, jobs_device, h, w, mask_channels, ksize);
     return pg::launch_status();
+}
+
+PG_EXPORT int pg_patch_compose_ordered_u8(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, void* stream) {
+    return pg_patch_compose_ordered_u8_k(jobs_device, njobs, h, w, mask_channels, 8, stream);
 }
 
 PG_EXPORT int pg_warp_perspective_u8(const pg_warp_job* jobs_device, int njobs, int max_dst_pixels, void* stream) {
@@ -137,11 +149,23 @@ PG_EXPORT int pg_warp_perspective_u8(const pg_warp_job* jobs_device, int njobs, 
     return pg::launch_status();
 }
 
-PG_EXPORT int pg_patch_compose_u8(const uint8_t* patch, const uint8_t* mask, uint8_t* canvas, uint8_t* canvas2, int h, int w, int mask_channels, void* stream) {
+PG_EXPORT int pg_patch_compose_u8_k(const uint8_t* patch, const uint8_t* mask, uint8_t* canvas, uint8_t* canvas2, int h, int w, int mask_channels, int ksize,
+                                    void* stream) {
     if (!patch || !mask || !canvas || h <= 0 || w <= 0 || mask_channels <= 0) return PG_ERR_INVALID_ARG;
+    if (ksize < 1 || ksize > 16) return PG_ERR_INVALID_ARG;
     if ((int64_t)h * w > 0x3fffffffLL) return PG_ERR_TOO_LARGE;
     int bx = (h * w + 255) / 256;
     if (bx > pg::max_stream_blocks()) bx = pg::max_stream_blocks();
-    hipLaunchKernelGGL(patch_compose_u8_kernel, dim3((unsigned)bx), dim3(256), 0, (hipStream_t)stream, patch, mask, canvas, canvas2, h, w, mask_channels);
+    const hipStream_t st = (hipStream_t)stream;
+    if (ksize == 8)
+        hipLaunchKernelGGL(patch_compose_u8_kernel<8>, dim3((unsigned)bx), dim3(256), 0, st, patch, mask, canvas, canvas2, h, w, mask_channels, 8);
+    else if (ksize == 5)
+        hipLaunchKernelGGL(patch_compose_u8_kernel<5>, dim3((unsigned)bx), dim3(256), 0, st, patch, mask, canvas, canvas2, h, w, mask_channels, 5);
+    else
+        hipLaunchKernelGGL(patch_compose_u8_kernel<0>, dim3((unsigned)bx), dim3(256), 0, st, patch, mask, canvas, canvas2, h, w, mask_channels, ksize);
     return pg::launch_status();
+}
+
+PG_EXPORT int pg_patch_compose_u8(const uint8_t* patch, const uint8_t* mask, uint8_t* canvas, uint8_t* canvas2, int h, int w, int mask_channels, void* stream) {
+    return pg_patch_compose_u8_k(patch, mask, canvas, canvas2, h, w, mask_channels, 8, stream);
 }

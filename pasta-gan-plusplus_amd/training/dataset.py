@@ -1,6 +1,7 @@
-"""Test-time loader of try-on pairs (BASELINE config 1; reference training/dataset.py:1952-2726,
-``UvitonDatasetFull_512_test_upper``): reads the reference's file formats and produces the 16-tuple its ``__getitem__``
-returns (:2702-2726) -- uint8 CHW arrays
+"""Test-time loader of try-on pairs (BASELINE config 1): the reference's three test sets, chosen by ``part=`` as test.py's
+``--testpart`` chooses them -- 'upper' ``UvitonDatasetFull_512_test_upper`` (training/dataset.py:1952-2728), 'lower'
+``UvitonDatasetFull_512_test_lower`` (:2729-3456), 'full' ``UvitonDatasetFull_512_test_full`` (:1251-1951).  Reads the reference's
+file formats and produces the 16-tuple every one of them returns (:2702-2726, :3456-3482, :1925-1950) -- uint8 CHW arrays
 
     image[3,512,512] clothes[3,512,512] pose[3,512,512] clothes_pose[3,512,512] norm_img[30,128,128] norm_img_lower[15,128,128]
     denorm_upper_img[3,512,512] denorm_lower_img[3,512,512] denorm_upper_mask[1,512,512] denorm_lower_mask[1,512,512]
@@ -146,12 +147,19 @@ def _garment_classes(parsing):
 
 
 class TryOnTestSet(torch.utils.data.Dataset):
-    """``UvitonDatasetFull_512_test_upper`` of the reference: transfer the UPPER garment of `clothes_name` onto `person_name`."""
+    """The reference's test sets: transfer the garment(s) of `clothes_name` onto `person_name`.
 
-    def __init__(self, path, test_txt='test_pairs.txt', use_sleeve_mask=False, device='cpu'):
+    part='upper' (default): the clothes' top (``UvitonDatasetFull_512_test_upper``); the person keeps the lower garment.
+    part='lower': the clothes' trousers or skirt (``UvitonDatasetFull_512_test_lower``); the person keeps the top.
+    part='full': the clothes' whole outfit (``UvitonDatasetFull_512_test_full``).
+    use_sleeve_mask reads the garment parsing of the image the upper garment comes from: the clothes' (upper, full) or the person's (lower)."""
+
+    def __init__(self, path, test_txt='test_pairs.txt', use_sleeve_mask=False, device='cpu', part='upper'):
         if PIL is None:
             raise ImportError('TryOnTestSet needs Pillow')
-        self.path, self.use_sleeve_mask, self.device = path, use_sleeve_mask, device
+        if part not in patch_routing.MODES:
+            raise ValueError(f'part must be one of {sorted(patch_routing.MODES)}, not {part!r}')
+        self.path, self.use_sleeve_mask, self.device, self.part = path, use_sleeve_mask, device, part
         self.pairs = []
         with open(os.path.join(path, test_txt)) as f:
             for line in f:
@@ -225,8 +233,9 @@ class TryOnTestSet(torch.utils.data.Dataset):
         return out[..., None].astype(np.uint8)
 
     # ------------------------------------------------------------------ one pair
-    def __getitem__(self, idx):
-        clothes_name, person_name = self.pairs[idx]
+    def _person(self, person_name):
+        """The person side every mode shares (dataset.py:2031-2080 = :1330-1375 = :2807-2852): padded image, pose map and keypoints,
+        parsing, retain mask, skin average."""
         raw = self._image(person_name)
         assert raw.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
         image, left = _pad_square(raw, 255)
@@ -244,7 +253,31 @@ class TryOnTestSet(torch.utils.data.Dataset):
             vals = vals[vals > 0]
             medians.append(np.median(vals) if vals.size else np.nan)
         skin_average = np.stack([np.full((SIDE, SIDE), m) for m in medians], axis=2)
+        return image, pose, kp, parsing, retain_mask, skin_average
 
+    def _clothes(self, clothes_name):
+        """The clothes side every mode shares: padded image, pose map and keypoints, parsing."""
+        craw = self._image(clothes_name)
+        clothes, left = _pad_square(craw, 255)
+        clothes_pose, ckp = self.pose_map(self._keypoints(clothes_name), craw.shape[:2])
+        clothes_pose, _ = _pad_square(clothes_pose, 0)
+        ckp[:, 0] += left
+        cparsing, _ = _pad_square(self._labels('parsing', clothes_name), 0)
+        return clothes, clothes_pose, ckp, cparsing
+
+    def _sleeve(self, name):
+        if not self.use_sleeve_mask:
+            return None
+        gp, _ = _pad_square(self._labels('garment_parsing', name), 0)
+        return np.isin(gp, (10, 11)).astype(np.uint8)
+
+    def __getitem__(self, idx):
+        clothes_name, person_name = self.pairs[idx]
+        return getattr(self, '_item_' + self.part)(clothes_name, person_name)
+
+    def _item_upper(self, clothes_name, person_name):
+        """dataset.py:2030-2224."""
+        image, pose, kp, parsing, retain_mask, skin_average = self._person(person_name)
         tops, dresses, pants, skirt = _garment_classes(parsing)
         lower_mask = skirt + pants
         lower_image = lower_mask * image
@@ -258,22 +291,14 @@ class TryOnTestSet(torch.utils.data.Dataset):
         elif lower_bbox is not None:
             bound[lower_bbox[1]:] += 255
 
-        craw = self._image(clothes_name)
-        clothes, _ = _pad_square(craw, 255)
-        clothes_pose, ckp = self.pose_map(self._keypoints(clothes_name), craw.shape[:2])
-        clothes_pose, _ = _pad_square(clothes_pose, 0)
-        ckp[:, 0] += left
-        cparsing, _ = _pad_square(self._labels('parsing', clothes_name), 0)
+        clothes, clothes_pose, ckp, cparsing = self._clothes(clothes_name)
         ctops, cdresses, _, _ = _garment_classes(cparsing)
         upper_mask = ctops + cdresses
         upper_image = upper_mask * clothes
         if cdresses.sum() > 0:                               # a dress replaces the person's lower garment entirely
             lower_mask, pants, skirt, lower_image, bound = lower_mask * 0, pants * 0, skirt * 0, lower_image * 0, bound * 0
         upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
-        sleeve = None
-        if self.use_sleeve_mask:
-            gp, _ = _pad_square(self._labels('garment_parsing', clothes_name), 0)
-            sleeve = np.isin(gp, (10, 11)).astype(np.uint8)
+        sleeve = self._sleeve(clothes_name)
 
         routed = patch_routing.normalize(upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8),
                                          sleeve, ckp, kp, 2, device=self.device)
@@ -284,8 +309,72 @@ class TryOnTestSet(torch.utils.data.Dataset):
         if upper_bbox is not None:
             bound[0:upper_bbox[3]] *= 0
         label = 0.0 if pants.sum() > 0 else (1.0 if skirt.sum() > 0 else (2.0 if cdresses.sum() > 0 else 1.0))
-        lower_label_map = np.full((SIDE, SIDE, 1), label / 2.0 * 255)
+        return self._pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
+                          person_name, clothes_name)
 
+    def _item_lower(self, clothes_name, person_name):
+        """dataset.py:2806-2981: the person keeps the top (re-pasted with an 8 x 8 eroded edge), the clothes' lower garment is routed."""
+        image, pose, kp, parsing, retain_mask, skin_average = self._person(person_name)
+        tops, dresses, pants, skirt = _garment_classes(parsing)                                # the PERSON's garment classes
+        upper_mask = tops + dresses
+        upper_image = upper_mask * image
+        lower_bbox = _bbox((skirt + pants).copy())
+        bound = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)
+        if lower_bbox is not None:                           # start of the lower garment: the person's own one (no hip rule here)
+            bound[lower_bbox[1]:] += 255
+        sleeve = self._sleeve(person_name)                   # the person's garment parsing: the top stays the person's
+
+        clothes, clothes_pose, ckp, cparsing = self._clothes(clothes_name)
+        _, _, cpants, cskirt = _garment_classes(cparsing)
+        lower_mask = cskirt + cpants
+        lower_image = lower_mask * clothes
+        if dresses.sum() > 0:                                # a person in a dress keeps it: nothing of the clothes' lower garment is routed
+            cskirt, cpants, lower_mask, lower_image, bound = cskirt * 0, cpants * 0, lower_mask * 0, lower_image * 0, bound * 0
+        upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
+
+        routed = patch_routing.normalize(upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8),
+                                         sleeve, ckp, kp, 2, device=self.device, part='lower')
+        norm_img, norm_img_lower, _, denorm_lower = (t.cpu().numpy() for t in routed)
+        denorm_upper = upper_image * _erode_white(upper_rgb.astype(np.uint8))                  # the person's own top, edge eroded (8 x 8)
+
+        label = 0.0 if cpants.sum() > 0 else (1.0 if cskirt.sum() > 0 else (2.0 if dresses.sum() > 0 else 1.0))
+        return self._pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper.astype(np.uint8), denorm_lower, retain_mask,
+                          skin_average, label, bound, person_name, clothes_name)
+
+    def _item_full(self, clothes_name, person_name):
+        """dataset.py:1329-1464: both garments come from the clothes image, the garment classes from the CLOTHES' parsing."""
+        image, pose, kp, parsing, retain_mask, skin_average = self._person(person_name)
+        clothes, clothes_pose, ckp, cparsing = self._clothes(clothes_name)
+        ctops, cdresses, cpants, cskirt = _garment_classes(cparsing)
+        upper_mask, lower_mask = ctops + cdresses, cskirt + cpants
+        upper_image, lower_image = upper_mask * clothes, lower_mask * clothes
+        upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
+        sleeve = self._sleeve(clothes_name)
+
+        routed = patch_routing.normalize(upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8),
+                                         sleeve, ckp, kp, 2, device=self.device, part='full')
+        norm_img, norm_img_lower, denorm_upper, denorm_lower = (t.cpu().numpy() for t in routed)
+
+        bound = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)    # start of the lower garment: the routed one's top row
+        lower_bbox = _bbox((denorm_lower.sum(axis=2, keepdims=True) > 0).astype(np.uint8))
+        if lower_bbox is not None:
+            bound[lower_bbox[1]:] += 255
+        if cpants.sum() > 0:
+            label = 0.0
+        elif cskirt.sum() > 0:
+            label = 1.0
+        elif cdresses.sum() > 0:                             # a dress as the outfit: no lower garment, no bound
+            label, bound = 2.0, bound * 0
+        else:
+            label = 1.0
+        return self._pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
+                          person_name, clothes_name)
+
+    @staticmethod
+    def _pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
+              person_name, clothes_name):
+        """The 16-tuple of ``__getitem__`` (dataset.py:2702-2726)."""
+        lower_label_map = np.full((SIDE, SIDE, 1), label / 2.0 * 255)
         chw = lambda a: np.ascontiguousarray(np.transpose(a, (2, 0, 1)))
         denorm_upper, denorm_lower = chw(denorm_upper), chw(denorm_lower.astype(np.uint8))
         return (chw(image), chw(clothes), chw(pose), chw(clothes_pose), chw(norm_img), chw(norm_img_lower), denorm_upper, denorm_lower,

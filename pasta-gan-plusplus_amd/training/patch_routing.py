@@ -9,8 +9,21 @@ as three batched launches of ``patch_routing_plugin`` (csrc/patch_routing.hip) p
 2. every patch -> canvas warp (up to 30 jobs, 512x512) in one launch,
 3. the erode-and-paste of each part, in the reference's order (later parts overwrite earlier ones).
 
-Images are uint8 HxWx3 tensors on the GPU (NumPy arrays are uploaded); the five results have the reference's shapes and dtype.
+Images are uint8 HxWx3 tensors on the GPU (NumPy arrays are uploaded); the results have the reference's shapes and dtype.
 GPU tensors run the HIP kernels; CPU tensors (device='cpu': BASELINE config 1, the loader without a GPU) the same arithmetic in NumPy.
+
+The reference's three try-on modes (test.py --testpart) route the same ten parts and differ in four decisions only (`part=`, MODES):
+
+========  ========================  ========================  ======  ===========================  ==========================
+part      upper-garment warp        lower-garment warp        erode   lower parts minus upper       results
+========  ========================  ========================  ======  ===========================  ==========================
+upper     clothes crop (:2605)      person crop (:2634)       8 x 8   torso / hips (:2654-2663)    5 (+ denorm_upper_img_wo_sleeve)
+lower     person crop (:3361)       clothes crop (:3388)      5 x 5   torso / hips (:3408-3417)    4
+full      clothes crop (:1843)      clothes crop (:1869)      5 x 5   no                           4
+========  ========================  ========================  ======  ===========================  ==========================
+
+(upper: dataset.py:2555-2700 ``UvitonDatasetFull_512_test_upper.normalize``; lower: :3313-3454; full: :1796-1923.)  Every
+de-normalising warp uses the person crop's inverse; the missing-sleeve mirroring is the same in all three.
 """
 
 import ctypes
@@ -27,6 +40,15 @@ BPARTS = [["rshoulder", "rhip", "lhip", "lshoulder"], ["lshoulder", "rshoulder",
           ["rshoulder", "relbow"], ["relbow", "rwrist"], ["lhip", "lknee"], ["lknee", "lankle"], ["rhip", "rknee"], ["rknee", "rankle"]]
 SLEEVE_PARTS = (2, 3, 4, 5)
 _J = {name: i for i, name in enumerate(ORDER)}
+# part -> (upper garment warped with the clothes crop?, lower garment warped with the clothes crop?, erode window, lower parts give way to the upper
+# garment?, denorm_upper_img_wo_sleeve returned?)
+MODES = {'upper': (True, False, 8, True, True), 'lower': (False, True, 5, True, False), 'full': (True, True, 5, False, False)}
+
+
+def _mode(part):
+    if part not in MODES:
+        raise ValueError(f"patch_routing: part must be one of {sorted(MODES)}, not {part!r}")
+    return MODES[part]
 
 
 class WarpJob(ctypes.Structure):
@@ -60,6 +82,10 @@ def _init():
         lib.pg_patch_compose_u8.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
         lib.pg_patch_compose_ordered_u8.restype = ctypes.c_int
         lib.pg_patch_compose_ordered_u8.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+        lib.pg_patch_compose_u8_k.restype = ctypes.c_int
+        lib.pg_patch_compose_u8_k.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+        lib.pg_patch_compose_ordered_u8_k.restype = ctypes.c_int
+        lib.pg_patch_compose_ordered_u8_k.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
         _plugin = plugin
     return _plugin
 
@@ -260,16 +286,17 @@ def _warp_perspective_cpu(src, m, wh):
     return torch.from_numpy(out[:, :, 0] if squeeze else out)
 
 
-def _patch_compose_cpu_(canvas, patch, mask, canvas2):
-    """`patch_compose_u8_kernel` in NumPy: paste where every in-range tap of the 8x8 window anchored at (4, 4) is 255."""
+def _patch_compose_cpu_(canvas, patch, mask, canvas2, ksize=8):
+    """`patch_compose_u8_kernel` in NumPy: paste where every in-range tap of the k x k window anchored at (k/2, k/2) is 255."""
     m = mask.numpy()
     m = (m[:, :, 0] if m.ndim == 3 else m) == 255
     h, w = m.shape
-    pad = np.ones((h + 8, w + 8), dtype=bool)                                    # out-of-image taps are ignored = count as white
-    pad[4:4 + h, 4:4 + w] = m
+    a = ksize // 2
+    pad = np.ones((h + ksize, w + ksize), dtype=bool)                            # out-of-image taps are ignored = count as white
+    pad[a:a + h, a:a + w] = m
     keep = np.ones((h, w), dtype=bool)
-    for ky in range(8):
-        for kx in range(8):
+    for ky in range(ksize):
+        for kx in range(ksize):
             keep &= pad[ky:ky + h, kx:kx + w]
     sel = torch.from_numpy(keep)[:, :, None]
     canvas.copy_(torch.where(sel, patch, canvas))
@@ -317,10 +344,12 @@ def warp_perspective_batch(jobs):
     return outs
 
 
-def patch_compose_(canvas, patch, mask, canvas2=None):
-    """canvas[p] = patch[p] where erode8x8(mask[..., 0]) == 255 (also into canvas2), in place."""
+def patch_compose_(canvas, patch, mask, canvas2=None, ksize=8):
+    """canvas[p] = patch[p] where erode_kxk(mask[..., 0]) == 255 (also into canvas2), in place; k = ksize (8: the upper mode's, 5: the others')."""
+    if not 1 <= ksize <= 16:
+        raise nat.NativeOpError(f'patch_routing: erode window {ksize} outside 1..16')
     if canvas.device.type != 'cuda':
-        return _patch_compose_cpu_(canvas, patch, mask, canvas2)
+        return _patch_compose_cpu_(canvas, patch, mask, canvas2, ksize)
     if traffic_counter is not None:     # patch + mask read, the canvas (and its copy) written where the eroded mask is set: counted whole
         traffic_counter['bytes'] += int(patch.numel()) + int(mask.numel()) + int(canvas.numel()) * (2 if canvas2 is not None else 1)
         traffic_counter['launches'] += 1
@@ -328,15 +357,21 @@ def patch_compose_(canvas, patch, mask, canvas2=None):
     h, w = canvas.shape[:2]
     mc = mask.shape[2] if mask.ndim == 3 else 1
     with torch.cuda.device(canvas.device):
-        st = lib.pg_patch_compose_u8(patch.data_ptr(), mask.data_ptr(), canvas.data_ptr(), canvas2.data_ptr() if canvas2 is not None else None,
-                                     int(h), int(w), int(mc), nat.stream_of(canvas))
-    nat.check(st, 'pg_patch_compose_u8')
+        st = lib.pg_patch_compose_u8_k(patch.data_ptr(), mask.data_ptr(), canvas.data_ptr(), canvas2.data_ptr() if canvas2 is not None else None,
+                                       int(h), int(w), int(mc), int(ksize), nat.stream_of(canvas))
+    nat.check(st, 'pg_patch_compose_u8_k')
     return canvas
 
 
-def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, sleeve_mask, clothes_keypoints, person_keypoints, box_factor, device='cuda'):
-    """The reference's ``normalize`` (dataset.py:2555-2700): returns (img [h,w,30], img_lower [h,w,15], denorm_upper_img,
-    denorm_upper_img_wo_sleeve, denorm_lower_img) as uint8 GPU tensors."""
+def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, sleeve_mask, clothes_keypoints, person_keypoints, box_factor, device='cuda',
+              part='upper'):
+    """The reference's ``normalize`` of try-on mode `part` (module docstring), as uint8 tensors on `device`:
+
+    part='upper' (dataset.py:2555-2700): (img [h,w,30], img_lower [h,w,15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img)
+    part='lower' (:3313-3454) and part='full' (:1796-1923): (img [h,w,30], img_lower [h,w,15], denorm_upper_img, denorm_lower_img)
+
+    (h, w = H / 2**box_factor, W / 2**box_factor; the canvases are [H, W, 3].)"""
+    up_by_clothes, lo_by_clothes, ksize, lower_minus_upper, wo_sleeve = _mode(part)
     dev = torch.device(device)
     up, lo = _gpu_u8(upper_img, dev), _gpu_u8(lower_img, dev)
     um, lm = _gpu_u8(upper_clothes_mask, dev), _gpu_u8(lower_clothes_mask, dev)
@@ -354,16 +389,18 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
         ar = 0.5 if ii < 6 else 0.4
         crops.append((get_crop(clothes_keypoints, bpart, wh, o_w, o_h, ar), get_crop(person_keypoints, bpart, wh, o_w, o_h, ar)))
 
-    # stage 1: image -> patch
+    # stage 1: image -> patch (the upper / lower garment through the clothes' or the person's crop, as the mode says)
+    up_m = [c[0][0] if up_by_clothes else c[1][0] for c in crops]
+    lo_m = [c[0][0] if lo_by_clothes else c[1][0] for c in crops]
     jobs, slot = [], {}
-    for ii, ((c_m, _), (p_m, _)) in enumerate(crops):
-        if c_m is not None:
+    for ii in range(10):
+        if up_m[ii] is not None:
             img_s, mask_s = src_sleeve if ii in SLEEVE_PARTS else src_body
             slot[('img', ii)], slot[('mask', ii)] = len(jobs), len(jobs) + 1
-            jobs += [(img_s, c_m, (w, h)), (mask_s, c_m, (w, h))]
-        if (ii == 0 or ii >= 6) and p_m is not None:
+            jobs += [(img_s, up_m[ii], (w, h)), (mask_s, up_m[ii], (w, h))]
+        if (ii == 0 or ii >= 6) and lo_m[ii] is not None:
             slot[('img_lower', ii)], slot[('mask_lower', ii)] = len(jobs), len(jobs) + 1
-            jobs += [(lo, p_m, (w, h)), (lm, p_m, (w, h))]
+            jobs += [(lo, lo_m[ii], (w, h)), (lm, lo_m[ii], (w, h))]
     out1 = warp_perspective_batch(jobs)
     zeros = lambda: torch.zeros([h, w, 3], dtype=torch.uint8, device=dev)
     get = lambda kind, ii: out1[slot[(kind, ii)]] if (kind, ii) in slot else zeros()
@@ -375,11 +412,11 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
 
     # stage 2: patch -> canvas
     jobs, slot2 = [], {}
-    for ii, ((c_m, _), (p_m, p_inv)) in enumerate(crops):
-        if c_m is not None and p_inv is not None:
+    for ii, (_, (_, p_inv)) in enumerate(crops):
+        if up_m[ii] is not None and p_inv is not None:
             slot2[('up', ii)] = len(jobs)
             jobs += [(part_imgs[ii], p_inv, (o_w, o_h)), (part_masks[ii], p_inv, (o_w, o_h))]
-        if (ii == 0 or ii >= 6) and p_m is not None and p_inv is not None:
+        if (ii == 0 or ii >= 6) and lo_m[ii] is not None and p_inv is not None:
             k = lower_ids.index(ii)
             slot2[('lo', ii)] = len(jobs)
             jobs += [(part_imgs_lower[k], p_inv, (o_w, o_h)), (part_masks_lower[k], p_inv, (o_w, o_h))]
@@ -387,18 +424,18 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
 
     # stage 3: erode + paste, in part order
     denorm_upper = torch.zeros_like(up)
-    denorm_upper_wo_sleeve = torch.zeros_like(up)
+    denorm_upper_wo_sleeve = torch.zeros_like(up) if wo_sleeve else None
     denorm_lower = torch.zeros_like(up)
     for ii in range(10):
         if ('up', ii) in slot2:
             k = slot2[('up', ii)]
-            patch_compose_(denorm_upper, out2[k], out2[k + 1], None if ii in SLEEVE_PARTS else denorm_upper_wo_sleeve)
+            patch_compose_(denorm_upper, out2[k], out2[k + 1], None if ii in SLEEVE_PARTS else denorm_upper_wo_sleeve, ksize)
         if ('lo', ii) in slot2:
             k = slot2[('lo', ii)]
-            patch_compose_(denorm_lower, out2[k], out2[k + 1])
+            patch_compose_(denorm_lower, out2[k], out2[k + 1], None, ksize)
 
-    # lower-garment parts give way to the upper garment; a missing sleeve is mirrored from the other side (:2655-2693)
-    for lower_i, upper_i in ((0, 0), (1, 6), (3, 8)):
+    # lower-garment parts give way to the upper garment (upper / lower modes); a missing sleeve is mirrored from the other side (:2655-2693)
+    for lower_i, upper_i in ((0, 0), (1, 6), (3, 8)) if lower_minus_upper else ():
         keep = 1 - (part_masks[upper_i].to(torch.int32).sum(dim=2, keepdim=True) > 0).to(torch.uint8)
         part_imgs_lower[lower_i] = part_imgs_lower[lower_i] * keep
         part_masks_lower[lower_i] = part_masks_lower[lower_i] * keep
@@ -414,7 +451,9 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
     part_imgs[3], part_masks[3] = torch.where(c35, flip(i3), i3), torch.where(c35, flip(m5), m3)     # as written in the reference: the image mirrored is part 3's own
     part_imgs[5], part_masks[5] = torch.where(c53, flip(i5), i5), torch.where(c53, flip(m3), m5)
 
-    return torch.cat(part_imgs, dim=2), torch.cat(part_imgs_lower, dim=2), denorm_upper, denorm_upper_wo_sleeve, denorm_lower
+    if wo_sleeve:
+        return torch.cat(part_imgs, dim=2), torch.cat(part_imgs_lower, dim=2), denorm_upper, denorm_upper_wo_sleeve, denorm_lower
+    return torch.cat(part_imgs, dim=2), torch.cat(part_imgs_lower, dim=2), denorm_upper, denorm_lower
 
 
 def _upload_table(arr, dev):
@@ -422,19 +461,22 @@ def _upload_table(arr, dev):
     return torch.from_numpy(arr.view(np.uint8).reshape(-1)).pin_memory().to(dev, non_blocking=True)
 
 
-def normalize_batch(samples, box_factor, device='cuda'):
+def normalize_batch(samples, box_factor, device='cuda', part='upper'):
     """`normalize` of a whole batch with THREE native launches instead of ~17 per sample: one image -> patch warp launch and one
     patch -> canvas warp launch over every job of every sample, one ordered erode-and-paste launch over every canvas (pg_patch_compose_ordered_u8), the
     homographies of all samples from one batched solve and the bookkeeping around them as a handful of batched tensor operations.
 
     samples: list of (upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, sleeve_mask | None, clothes_keypoints, person_keypoints), images uint8
-    [H, W, 3] (all the same size).  Returns the five results of `normalize`, stacked: img [N, h, w, 30], img_lower [N, h, w, 15], denorm_upper_img,
-    denorm_upper_img_wo_sleeve, denorm_lower_img [N, H, W, 3] -- bit-identical to the per-sample calls (tests/test_patch_routing.py)."""
+    [H, W, 3] (all the same size).  Returns the results of `normalize(..., part=part)`, stacked -- part='upper': img [N, h, w, 30], img_lower
+    [N, h, w, 15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img [N, H, W, 3]; part='lower' / 'full': the same without
+    denorm_upper_img_wo_sleeve -- bit-identical to the per-sample calls (tests/test_patch_routing.py, tests/test_routing_modes_gpu.py).  Every mode is the
+    same three launches; the mode only picks which crop warps which garment, the erode window and the masking of the lower parts."""
+    up_by_clothes, lo_by_clothes, ksize, lower_minus_upper, wo_sleeve = _mode(part)
     dev = torch.device(device)
     n = len(samples)
     if dev.type != 'cuda':
-        outs = [normalize(*s, box_factor, device=device) for s in samples]
-        return tuple(torch.stack([o[i] for o in outs]) for i in range(5))
+        outs = [normalize(*s, box_factor, device=device, part=part) for s in samples]
+        return tuple(torch.stack([o[i] for o in outs]) for i in range(len(outs[0])))
     lib = _init().lib
     ups = torch.stack([_gpu_u8(s[0], dev) for s in samples])
     los = torch.stack([_gpu_u8(s[1], dev) for s in samples])
@@ -446,7 +488,7 @@ def normalize_batch(samples, box_factor, device='cuda'):
     with_sleeve = [i for i, s in enumerate(samples) if s[4] is not None]
     if with_sleeve:
         sl = torch.stack([_gpu_u8(samples[i][4], dev) for i in with_sleeve])
-        u_s, m_s = ups[with_sleeve], ums[with_sleeve]
+        u_s, m_s = torch.stack([ups[i] for i in with_sleeve]), torch.stack([ums[i] for i in with_sleeve])
         sleeve_img, sleeve_msk, body_img, body_msk = u_s * sl, m_s * sl, u_s * (1 - sl), m_s * (1 - sl)
     pos = {i: k for k, i in enumerate(with_sleeve)}
 
@@ -473,6 +515,7 @@ def normalize_batch(samples, box_factor, device='cuda'):
     c_m = {k: invs[j] for j, k in enumerate(ckeys)}
     p_m = {k: invs[len(ckeys) + j] for j, k in enumerate(pkeys)}
     p_inv = {k: invs[len(ckeys) + len(pkeys) + j] for j, k in enumerate(pkeys)}
+    up_m, lo_m = (c_m if up_by_clothes else p_m), (c_m if lo_by_clothes else p_m)
 
     # ---- stage 1: image -> patch.  Slots of P1: part images 0..9, part masks 10..19, lower images 20..24, lower masks 25..29 (missing parts stay zero)
     lower_ids = [0, 6, 7, 8, 9]
@@ -483,19 +526,20 @@ def normalize_batch(samples, box_factor, device='cuda'):
     j1, j2 = [], []
     for i in range(n):
         for ii in range(10):
-            if (i, ii) in c_m:
+            if (i, ii) in up_m:
                 img_s, msk_s = sources(i, ii)
-                j1.append((img_s.data_ptr(), p1 + (i * 30 + ii) * s1, c_m[(i, ii)]))
-                j1.append((msk_s.data_ptr(), p1 + (i * 30 + 10 + ii) * s1, c_m[(i, ii)]))
+                j1.append((img_s.data_ptr(), p1 + (i * 30 + ii) * s1, up_m[(i, ii)]))
+                j1.append((msk_s.data_ptr(), p1 + (i * 30 + 10 + ii) * s1, up_m[(i, ii)]))
                 if (i, ii) in p_inv:
                     j2.append((p1 + (i * 30 + ii) * s1, p2 + (i * 30 + ii) * s2, p_inv[(i, ii)]))
                     j2.append((p1 + (i * 30 + 10 + ii) * s1, p2 + (i * 30 + 10 + ii) * s2, p_inv[(i, ii)]))
-            if (ii == 0 or ii >= 6) and (i, ii) in p_m:
+            if (ii == 0 or ii >= 6) and (i, ii) in lo_m:
                 k = lower_ids.index(ii)
-                j1.append((los[i].data_ptr(), p1 + (i * 30 + 20 + k) * s1, p_m[(i, ii)]))
-                j1.append((lms[i].data_ptr(), p1 + (i * 30 + 25 + k) * s1, p_m[(i, ii)]))
-                j2.append((p1 + (i * 30 + 20 + k) * s1, p2 + (i * 30 + 20 + k) * s2, p_inv[(i, ii)]))
-                j2.append((p1 + (i * 30 + 25 + k) * s1, p2 + (i * 30 + 25 + k) * s2, p_inv[(i, ii)]))
+                j1.append((los[i].data_ptr(), p1 + (i * 30 + 20 + k) * s1, lo_m[(i, ii)]))
+                j1.append((lms[i].data_ptr(), p1 + (i * 30 + 25 + k) * s1, lo_m[(i, ii)]))
+                if (i, ii) in p_inv:
+                    j2.append((p1 + (i * 30 + 20 + k) * s1, p2 + (i * 30 + 20 + k) * s2, p_inv[(i, ii)]))
+                    j2.append((p1 + (i * 30 + 25 + k) * s1, p2 + (i * 30 + 25 + k) * s2, p_inv[(i, ii)]))
 
     def warp_table(jobs, sh, sw, dh, dw):
         t = np.zeros(len(jobs), dtype=_WARP_DT)
@@ -517,34 +561,34 @@ def normalize_batch(samples, box_factor, device='cuda'):
                 traffic_counter['launches'] += 1
 
         # ---- stage 3: every canvas of the batch in one ordered erode-and-paste launch
-        D = torch.empty([3, n, o_h, o_w, 3], dtype=torch.uint8, device=dev)       # denorm_upper, denorm_upper_wo_sleeve, denorm_lower
+        nd = 3 if wo_sleeve else 2
+        D = torch.empty([nd, n, o_h, o_w, 3], dtype=torch.uint8, device=dev)      # denorm_upper, [denorm_upper_wo_sleeve,] denorm_lower
         d0 = D.data_ptr()
         ct = np.zeros(2 * n, dtype=_COMPOSE_DT)
         for i in range(n):
-            up_parts = [ii for ii in range(10) if (i, ii) in c_m and (i, ii) in p_inv]
-            lo_parts = [ii for ii in lower_ids if (i, ii) in p_m]
+            up_parts = [ii for ii in range(10) if (i, ii) in up_m and (i, ii) in p_inv]
+            lo_parts = [ii for ii in lower_ids if (i, ii) in lo_m and (i, ii) in p_inv]
             a, b = ct[2 * i], ct[2 * i + 1]
-            a['canvas'], a['canvas2'], a['nparts'] = d0 + i * s2, d0 + (n + i) * s2, len(up_parts)
+            a['canvas'], a['canvas2'], a['nparts'] = d0 + i * s2, d0 + (n + i) * s2 if wo_sleeve else 0, len(up_parts)
             for k, ii in enumerate(up_parts):
                 a['patch'][k], a['mask'][k], a['to_canvas2'][k] = p2 + (i * 30 + ii) * s2, p2 + (i * 30 + 10 + ii) * s2, int(ii not in SLEEVE_PARTS)
-            b['canvas'], b['canvas2'], b['nparts'] = d0 + (2 * n + i) * s2, 0, len(lo_parts)
+            b['canvas'], b['canvas2'], b['nparts'] = d0 + ((nd - 1) * n + i) * s2, 0, len(lo_parts)
             for k, ii in enumerate(lo_parts):
                 kk = lower_ids.index(ii)
                 b['patch'][k], b['mask'][k] = p2 + (i * 30 + 20 + kk) * s2, p2 + (i * 30 + 25 + kk) * s2
         tab = _upload_table(ct, dev)
         keep.append(tab)
-        nat.check(lib.pg_patch_compose_ordered_u8(tab.data_ptr(), 2 * n, o_h, o_w, 3, stream), 'pg_patch_compose_ordered_u8')
+        nat.check(lib.pg_patch_compose_ordered_u8_k(tab.data_ptr(), 2 * n, o_h, o_w, 3, ksize, stream), 'pg_patch_compose_ordered_u8_k')
         if traffic_counter is not None:
-            traffic_counter['bytes'] += int(sum(int(c_['nparts']) for c_ in ct)) * 2 * s2 + 3 * n * s2
+            traffic_counter['bytes'] += int(sum(int(c_['nparts']) for c_ in ct)) * 2 * s2 + nd * n * s2
             traffic_counter['launches'] += 1
 
-    # ---- the rest of `normalize` on the batched buffers: lower-garment parts give way to the upper garment; a missing sleeve is mirrored from the other side
-    imgs, masks, imgs_lo, masks_lo = P1[:, 0:10], P1[:, 10:20], P1[:, 20:25], P1[:, 25:30]
-    gone = (masks[:, [0, 6, 8]].to(torch.int32).sum(dim=4, keepdim=True) > 0)            # [N, 3, h, w, 1]
-    keep_lo = (~gone).to(torch.uint8)
-    idx = torch.tensor([0, 1, 3], device=dev)
-    imgs_lo = imgs_lo.index_copy(1, idx, imgs_lo[:, [0, 1, 3]] * keep_lo)
-    masks_lo = masks_lo.index_copy(1, idx, masks_lo[:, [0, 1, 3]] * keep_lo)
+    # ---- the rest of `normalize` on the batched buffers: lower-garment parts give way to the upper garment (upper / lower modes); a missing sleeve is
+    # mirrored from the other side
+    imgs, masks, imgs_lo = P1[:, 0:10], P1[:, 10:20], P1[:, 20:25]
+    if lower_minus_upper:           # (slices and stacks, no index lists: those would be host -> device copies, i.e. host syncs)
+        keep = lambda ii: (masks[:, ii].to(torch.int32).sum(dim=3, keepdim=True) == 0).to(torch.uint8)      # [N, h, w, 1]
+        imgs_lo = torch.stack([imgs_lo[:, 0] * keep(0), imgs_lo[:, 1] * keep(6), imgs_lo[:, 2], imgs_lo[:, 3] * keep(8), imgs_lo[:, 4]], dim=1)
     has = (masks != 0).flatten(2).any(dim=2)                                              # [N, 10]
     col = lambda t: t[:, None, None, None]
     flip = lambda t: torch.flip(t, dims=[2])                                              # [N, h, w, 3]: the width axis
@@ -555,4 +599,6 @@ def normalize_batch(samples, box_factor, device='cuda'):
                             torch.where(c53, flip(i5), i5), imgs[:, 6], imgs[:, 7], imgs[:, 8], imgs[:, 9]], dim=1)      # (parts 3 / 5: the image mirrored is the part's own, as in the reference)
     img = new_imgs.permute(0, 2, 3, 1, 4).reshape(n, h, w, 30)
     img_lower = imgs_lo.permute(0, 2, 3, 1, 4).reshape(n, h, w, 15)
-    return img, img_lower, D[0], D[1], D[2]
+    if wo_sleeve:
+        return img, img_lower, D[0], D[1], D[2]
+    return img, img_lower, D[0], D[1]
