@@ -2,7 +2,7 @@
  * pasta_gan_ops.h -- C ABI of the MI355X (gfx950) kernels behind PASTA-GAN++'s
  * generator-synthesis operator API.
  *
- * Five shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing):
+ * Seven shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing, the augment pipe and the try-on staging):
  *   bias_act_plugin.so      pg_bias_act
  *   upfirdn2d_plugin.so     pg_upfirdn2d, pg_upfirdn2d_bias_act, pg_upfirdn2d_with_odd_samples
  *   conv2d_plugin.so        fp32: pg_conv2d_{packed_size,pack_weight,forward,splitk_plan,forward_splitk}, pg_conv2d_winograd_*,
@@ -11,6 +11,7 @@
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
  *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color
+ *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -607,6 +608,45 @@ int pg_augment_warp_adjoint(const float* dy, float* workspace, float* dx, const 
                             int n, int c, int h, int w, void* stream);
 int pg_augment_color(const float* x, float* y, const float* mat, int n, int c, int hw, int mode, void* stream);
 int pg_augment_abi_version(void);
+
+/* tryon_plugin.so -- the staging on either side of the generator in the try-on driver (training/tryon.py; reference test.py:126-181).  Results equal
+ * torch's GPU arithmetic bit for bit (u / 127.5 is u * (1.0f / 127.5f), no fused multiply-adds).
+ * pg_tryon_row_extent_u8: canvases [ncanvases, h, w, channels] uint8 (16-byte aligned, w * channels % 16 == 0) -> extents int32 [ncanvases, 2]:
+ *   the first and last row holding a non-zero byte, -1 / -1 when the canvas is empty.  One launch.
+ * pg_tryon_inputs: the seven float32 NCHW inputs of training.dataset.to_generator_inputs for a batch of n, in one launch.  Sources are uint8 NHWC
+ *   (H x W canvases, h x w part patches; W, w multiples of 4; dword-aligned), outputs dense float32 NCHW (16-byte aligned).  The bound plane is
+ *   bound_rows[i, y] after the mode's post-routing rule: PG_TRYON_UPPER zeroes the rows above extents[i, 1] (the last row of
+ *   denorm_upper_img_wo_sleeve); PG_TRYON_FULL adds 255 (mod 256) from row extents[i, 0] on (the routed lower garment's first row) and zeroes the plane
+ *   when label[i] == 2 (a dress); PG_TRYON_LOWER takes the rows as they are (extents may be NULL).  An extent of -1 leaves the rows unchanged.
+ * pg_tryon_triptych_u8: finetune_img float32 [n, 3, H, W] + clothes, image uint8 [n, H, W, 3] -> out uint8 [n, H, 3 cw, 3]: columns x0 : x0 + cw of
+ *   clothes | person | result.  result = clip((x + 1) * 127.5, 0, 255) truncated, NaN -> 0; clothes / person = ((u / 127.5 - 1) + 1) * 127.5 truncated
+ *   (the reference's round trip, unclipped: it can be one below u).  x0, cw, W multiples of 4. */
+enum pg_tryon_mode { PG_TRYON_UPPER = 0, PG_TRYON_LOWER = 1, PG_TRYON_FULL = 2 };
+typedef struct pg_tryon_io {
+    const unsigned char* image;            /* [n, H, W, 3] */
+    const unsigned char* pose;             /* [n, H, W, 3] */
+    const unsigned char* retain_mask;      /* [n, H, W, 1] */
+    const unsigned char* denorm_upper;     /* [n, H, W, 3] */
+    const unsigned char* denorm_lower;     /* [n, H, W, 3] */
+    const unsigned char* norm_img;         /* [n, h, w, 30] */
+    const unsigned char* norm_img_lower;   /* [n, h, w, 15] */
+    const float* skin;                     /* [n, 3]: the skin medians (float32, NaN kept) */
+    const int* label;                      /* [n]: 0, 1 or 2 */
+    const unsigned char* bound_rows;       /* [n, H]: the host part of lower_clothes_upper_bound, one value per row */
+    const int* extents;                    /* [n, 2] from pg_tryon_row_extent_u8 (upper: of denorm_upper_img_wo_sleeve; full: of the routed lower garment) */
+    float* c;                              /* [n, 45, h, w] */
+    float* retain;                         /* [n, 6, H, W] */
+    float* pose_out;                       /* [n, 5, H, W] */
+    float* denorm_upper_out;               /* [n, 3, H, W] */
+    float* denorm_lower_out;               /* [n, 3, H, W] */
+    float* upper_mask_out;                 /* [n, 1, H, W] */
+    float* lower_mask_out;                 /* [n, 1, H, W] */
+} pg_tryon_io;
+int pg_tryon_row_extent_u8(const unsigned char* canvases, int ncanvases, int h, int w, int channels, int* extents, void* stream);
+int pg_tryon_inputs(const pg_tryon_io* io, int n, int H, int W, int h, int w, int mode, void* stream);
+int pg_tryon_triptych_u8(const float* finetune_img, const unsigned char* clothes, const unsigned char* image, unsigned char* out, int n, int H, int W,
+                         int x0, int cw, void* stream);
+int pg_tryon_abi_version(void);
 
 #ifdef __cplusplus
 }

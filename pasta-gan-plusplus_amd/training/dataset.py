@@ -235,7 +235,7 @@ class TryOnTestSet(torch.utils.data.Dataset):
     # ------------------------------------------------------------------ one pair
     def _person(self, person_name):
         """The person side every mode shares (dataset.py:2031-2080 = :1330-1375 = :2807-2852): padded image, pose map and keypoints,
-        parsing, retain mask, skin average."""
+        parsing, retain mask, the three skin medians (NaN where the neck and face hold no pixel)."""
         raw = self._image(person_name)
         assert raw.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
         image, left = _pad_square(raw, 255)
@@ -252,8 +252,12 @@ class TryOnTestSet(torch.utils.data.Dataset):
             vals = skin[..., ch].reshape(-1)
             vals = vals[vals > 0]
             medians.append(np.median(vals) if vals.size else np.nan)
-        skin_average = np.stack([np.full((SIDE, SIDE), m) for m in medians], axis=2)
-        return image, pose, kp, parsing, retain_mask, skin_average
+        return image, pose, kp, parsing, retain_mask, medians
+
+    @staticmethod
+    def _skin_map(medians):
+        """skin_average [512, 512, 3] float64: the medians as constant planes (dataset.py:2079)."""
+        return np.stack([np.full((SIDE, SIDE), m) for m in medians], axis=2)
 
     def _clothes(self, clothes_name):
         """The clothes side every mode shares: padded image, pose map and keypoints, parsing."""
@@ -275,9 +279,33 @@ class TryOnTestSet(torch.utils.data.Dataset):
         clothes_name, person_name = self.pairs[idx]
         return getattr(self, '_item_' + self.part)(clothes_name, person_name)
 
-    def _item_upper(self, clothes_name, person_name):
-        """dataset.py:2030-2224."""
-        image, pose, kp, parsing, retain_mask, skin_average = self._person(person_name)
+    def unrouted(self, idx):
+        """Everything ``__getitem__`` computes except the patch routing and what depends on its result, for a batched route on the GPU
+        (training/tryon.py).  A dict of
+
+        upper_img, lower_img, upper_mask, lower_mask  uint8 [512, 512, 3]: the routing inputs of ``patch_routing.normalize_batch``
+        sleeve                                         uint8 [512, 512, 1] or None; clothes_kp, person_kp float64 [18, 3]
+        image, clothes, pose                           uint8 [512, 512, 3] as read (HWC); retain_mask uint8 [512, 512, 1]
+        skin                                           float64 [3]: the skin medians, NaN kept
+        label                                          int: 0, 1 or 2
+        bound                                          uint8 [512]: the host part of lower_clothes_upper_bound, one value per row (the bound is
+                                                       constant along each row in every mode); the upper and full modes finish it from the
+                                                       routed canvases (training.tryon.final_bound)
+        canvas                                         uint8 [512, 512, 3] or None: the mode's host-computed garment canvas -- the person's eroded
+                                                       lower garment (upper) or eroded top (lower); None in the full mode
+        person_name, clothes_name"""
+        clothes_name, person_name = self.pairs[idx]
+        h = getattr(self, '_host_' + self.part)(clothes_name, person_name)
+        up, lo, um, lm, sleeve, ckp, kp = h['routing']
+        return dict(upper_img=up, lower_img=lo, upper_mask=um, lower_mask=lm, sleeve=sleeve, clothes_kp=ckp, person_kp=kp, image=h['image'],
+                    clothes=h['clothes'], pose=h['pose'], retain_mask=h['retain_mask'], skin=np.array(h['medians'], dtype=np.float64),
+                    label=int(h['label']), bound=np.ascontiguousarray(h['bound'][:, 0, 0]), canvas=h['canvas'], person_name=person_name,
+                    clothes_name=clothes_name)
+
+    # ------------------------------------------------------------------ the three modes: host half (before the routing), then the rest
+    def _host_upper(self, clothes_name, person_name):
+        """dataset.py:2030-2224 up to the routing, plus what does not depend on it."""
+        image, pose, kp, parsing, retain_mask, medians = self._person(person_name)
         tops, dresses, pants, skirt = _garment_classes(parsing)
         lower_mask = skirt + pants
         lower_image = lower_mask * image
@@ -299,22 +327,26 @@ class TryOnTestSet(torch.utils.data.Dataset):
             lower_mask, pants, skirt, lower_image, bound = lower_mask * 0, pants * 0, skirt * 0, lower_image * 0, bound * 0
         upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
         sleeve = self._sleeve(clothes_name)
-
-        routed = patch_routing.normalize(upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8),
-                                         sleeve, ckp, kp, 2, device=self.device)
-        norm_img, norm_img_lower, denorm_upper, denorm_upper_wo_sleeve, _ = (t.cpu().numpy() for t in routed)
+        routing = (upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8), sleeve, ckp, kp)
         denorm_lower = lower_image * _erode_white(lower_rgb.astype(np.uint8))                  # the person's own lower garment, edge eroded
+        label = 0.0 if pants.sum() > 0 else (1.0 if skirt.sum() > 0 else (2.0 if cdresses.sum() > 0 else 1.0))
+        return dict(routing=routing, image=image, clothes=clothes, pose=pose, clothes_pose=clothes_pose, retain_mask=retain_mask, medians=medians,
+                    label=label, bound=bound, canvas=denorm_lower.astype(np.uint8))
 
+    def _item_upper(self, clothes_name, person_name):
+        h = self._host_upper(clothes_name, person_name)
+        routed = patch_routing.normalize(*h['routing'], 2, device=self.device)
+        norm_img, norm_img_lower, denorm_upper, denorm_upper_wo_sleeve, _ = (t.cpu().numpy() for t in routed)
+        bound = h['bound']
         upper_bbox = _bbox((denorm_upper_wo_sleeve.sum(axis=2, keepdims=True) > 0).astype(np.uint8))
         if upper_bbox is not None:
             bound[0:upper_bbox[3]] *= 0
-        label = 0.0 if pants.sum() > 0 else (1.0 if skirt.sum() > 0 else (2.0 if cdresses.sum() > 0 else 1.0))
-        return self._pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
-                          person_name, clothes_name)
+        return self._pack(h['image'], h['clothes'], h['pose'], h['clothes_pose'], norm_img, norm_img_lower, denorm_upper, h['canvas'], h['retain_mask'],
+                          self._skin_map(h['medians']), h['label'], bound, person_name, clothes_name)
 
-    def _item_lower(self, clothes_name, person_name):
+    def _host_lower(self, clothes_name, person_name):
         """dataset.py:2806-2981: the person keeps the top (re-pasted with an 8 x 8 eroded edge), the clothes' lower garment is routed."""
-        image, pose, kp, parsing, retain_mask, skin_average = self._person(person_name)
+        image, pose, kp, parsing, retain_mask, medians = self._person(person_name)
         tops, dresses, pants, skirt = _garment_classes(parsing)                                # the PERSON's garment classes
         upper_mask = tops + dresses
         upper_image = upper_mask * image
@@ -331,44 +363,53 @@ class TryOnTestSet(torch.utils.data.Dataset):
         if dresses.sum() > 0:                                # a person in a dress keeps it: nothing of the clothes' lower garment is routed
             cskirt, cpants, lower_mask, lower_image, bound = cskirt * 0, cpants * 0, lower_mask * 0, lower_image * 0, bound * 0
         upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
-
-        routed = patch_routing.normalize(upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8),
-                                         sleeve, ckp, kp, 2, device=self.device, part='lower')
-        norm_img, norm_img_lower, _, denorm_lower = (t.cpu().numpy() for t in routed)
+        routing = (upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8), sleeve, ckp, kp)
         denorm_upper = upper_image * _erode_white(upper_rgb.astype(np.uint8))                  # the person's own top, edge eroded (8 x 8)
-
         label = 0.0 if cpants.sum() > 0 else (1.0 if cskirt.sum() > 0 else (2.0 if dresses.sum() > 0 else 1.0))
-        return self._pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper.astype(np.uint8), denorm_lower, retain_mask,
-                          skin_average, label, bound, person_name, clothes_name)
+        return dict(routing=routing, image=image, clothes=clothes, pose=pose, clothes_pose=clothes_pose, retain_mask=retain_mask, medians=medians,
+                    label=label, bound=bound, canvas=denorm_upper.astype(np.uint8))
 
-    def _item_full(self, clothes_name, person_name):
+    def _item_lower(self, clothes_name, person_name):
+        h = self._host_lower(clothes_name, person_name)
+        routed = patch_routing.normalize(*h['routing'], 2, device=self.device, part='lower')
+        norm_img, norm_img_lower, _, denorm_lower = (t.cpu().numpy() for t in routed)
+        return self._pack(h['image'], h['clothes'], h['pose'], h['clothes_pose'], norm_img, norm_img_lower, h['canvas'], denorm_lower, h['retain_mask'],
+                          self._skin_map(h['medians']), h['label'], h['bound'], person_name, clothes_name)
+
+    def _host_full(self, clothes_name, person_name):
         """dataset.py:1329-1464: both garments come from the clothes image, the garment classes from the CLOTHES' parsing."""
-        image, pose, kp, parsing, retain_mask, skin_average = self._person(person_name)
+        image, pose, kp, parsing, retain_mask, medians = self._person(person_name)
         clothes, clothes_pose, ckp, cparsing = self._clothes(clothes_name)
         ctops, cdresses, cpants, cskirt = _garment_classes(cparsing)
         upper_mask, lower_mask = ctops + cdresses, cskirt + cpants
         upper_image, lower_image = upper_mask * clothes, lower_mask * clothes
         upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
         sleeve = self._sleeve(clothes_name)
-
-        routed = patch_routing.normalize(upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8),
-                                         sleeve, ckp, kp, 2, device=self.device, part='full')
-        norm_img, norm_img_lower, denorm_upper, denorm_lower = (t.cpu().numpy() for t in routed)
-
-        bound = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)    # start of the lower garment: the routed one's top row
-        lower_bbox = _bbox((denorm_lower.sum(axis=2, keepdims=True) > 0).astype(np.uint8))
-        if lower_bbox is not None:
-            bound[lower_bbox[1]:] += 255
+        routing = (upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8), sleeve, ckp, kp)
+        bound = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)    # start of the lower garment: the routed one's top row (after the routing)
         if cpants.sum() > 0:
             label = 0.0
         elif cskirt.sum() > 0:
             label = 1.0
         elif cdresses.sum() > 0:                             # a dress as the outfit: no lower garment, no bound
-            label, bound = 2.0, bound * 0
+            label = 2.0
         else:
             label = 1.0
-        return self._pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
-                          person_name, clothes_name)
+        return dict(routing=routing, image=image, clothes=clothes, pose=pose, clothes_pose=clothes_pose, retain_mask=retain_mask, medians=medians,
+                    label=label, bound=bound, canvas=None)
+
+    def _item_full(self, clothes_name, person_name):
+        h = self._host_full(clothes_name, person_name)
+        routed = patch_routing.normalize(*h['routing'], 2, device=self.device, part='full')
+        norm_img, norm_img_lower, denorm_upper, denorm_lower = (t.cpu().numpy() for t in routed)
+        bound = h['bound']
+        lower_bbox = _bbox((denorm_lower.sum(axis=2, keepdims=True) > 0).astype(np.uint8))
+        if lower_bbox is not None:
+            bound[lower_bbox[1]:] += 255
+        if h['label'] == 2.0:
+            bound = bound * 0
+        return self._pack(h['image'], h['clothes'], h['pose'], h['clothes_pose'], norm_img, norm_img_lower, denorm_upper, denorm_lower, h['retain_mask'],
+                          self._skin_map(h['medians']), h['label'], bound, person_name, clothes_name)
 
     @staticmethod
     def _pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
@@ -394,3 +435,26 @@ def to_generator_inputs(batch, device):
                 pose=torch.cat([unit(pose), unit(lower_label_map), unit(lower_bound)], dim=1),
                 denorm_upper_input=unit(den_up), denorm_lower_input=unit(den_lo),
                 denorm_upper_mask=den_up_mask.to(torch.float32), denorm_lower_mask=den_lo_mask.to(torch.float32))
+
+
+_UNROUTED_ARRAYS = ('upper_img', 'lower_img', 'upper_mask', 'lower_mask', 'sleeve', 'image', 'clothes', 'pose', 'retain_mask', 'bound', 'canvas')
+
+
+def collate_unrouted(items, pin=False):
+    """Stack ``TryOnTestSet.unrouted`` items into a batch: the uint8 arrays as [N, ...] tensors (pinned with pin=True -- only in the process that
+    owns the GPU; a DataLoader with workers pins them itself with ``pin_memory=True``), skin as float32 [N, 3] (the cast
+    ``skin_average.to(torch.float32)`` of test.py:133, NaN kept), label as int32 [N]; keypoints and names stay lists.  Keys whose value is None
+    (sleeve without the sleeve mask, canvas in the full mode) stay None."""
+    out = {}
+    for k in _UNROUTED_ARRAYS:
+        if items[0][k] is None:
+            out[k] = None
+            continue
+        t = torch.from_numpy(np.stack([it[k] for it in items]))
+        out[k] = t.pin_memory() if pin else t
+    skin = torch.from_numpy(np.stack([it['skin'] for it in items])).to(torch.float32)
+    label = torch.tensor([it['label'] for it in items], dtype=torch.int32)
+    out['skin'], out['label'] = (skin.pin_memory(), label.pin_memory()) if pin else (skin, label)
+    for k in ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'):
+        out[k] = [it[k] for it in items]
+    return out
