@@ -3,7 +3,10 @@
 (BASELINE.json config 2: SynthesisNetworkFull_v18, 512^2, N=8 per GPU, fp32, eval,
 random latents + style maps, noise_mode='const', argmax parsing path as test.py runs it).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the result line: nothing
+else.  --full adds what the headline figure does not need: `cpu_baseline` and `secondary` below.
 
 --dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/<name>.npy, at most 64 MB in all (dump_outputs());
 weights and inputs are seeded, so two builds given the same arguments can be compared output for output.
@@ -24,9 +27,9 @@ Extra objects on that line:
                   profiles/rNN_traffic_cfg2.json (rocprofv3 --pmc passes over this same command;
                   PMC counters cannot be read in-process) -- `traffic_source` names the file.
                   --mode bf16_1024 (config 5): dominant kernel = conv2d_mfma16, HBM-bound.
-  cpu_baseline -- the CPU oracle (oracle/network_ref.py, a port) timed on this host at N=1 on a
+  cpu_baseline -- (--full only) the CPU oracle (oracle/network_ref.py, a port) timed on this host at N=1 on a
                   bounded sample (rank 0, --gpus 1 only).
-  secondary    -- (--gpus 1, headline mode only) BASELINE configs 3, 5 and 4 (one-GPU share of the training step: batch 4, `--mode train`) run as
+  secondary    -- (--full only; --gpus 1, headline mode only) BASELINE configs 3, 5 and 4 (one-GPU share of the training step: batch 4, `--mode train`) run as
                   short child processes of the same script after the headline's timed region: their value / ms_per_step / roofline, so that
                   those numbers are driver-timed too (skipped under a profiler).
                   Headline fields are untouched by it.
@@ -409,7 +412,7 @@ def run_stack(args, rank, world, dev, dist):
                               eager_ms_per_step=round(1e3 * eager_elapsed / args.steps, 3),
                               conv_time_frac_of_step=round(t_dom / eager_elapsed, 4),   # its launches' event time / the wall time of the pass they were measured in
                               top_res_gbs=round(sum(r[3] for r in top) / max(sum(r[2] for r in top), 1e-12) / 1e9, 1)))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline_stack(args.channel_max)
     if args.conv_breakdown:
         groups = {}
@@ -592,7 +595,9 @@ def main():
     ap.add_argument('--steps', type=int, default=20)         # warm-up 5, time 20 iterations
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=BATCH_PER_GPU, help='images per GPU per step (config 2: 8)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: the CPU oracle baseline (`cpu_baseline`) and, '
+                                                        'in the headline mode, configs 3, 5 and 4 as child runs (`secondary`)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip `cpu_baseline`')
     ap.add_argument('--no-graph', action='store_true', help='config 5: time eager launches instead of hipGraph replays')
     ap.add_argument('--train-graphs', action='store_true', help='config 4: replay each phase as one hipGraph (TrainingStep(graphs=True)); measured 312 vs 304 ms eager -- the step is GPU-bound')
     ap.add_argument('--d-fp16-res', type=int, default=3, help='config 4: discriminator resolutions in fp16 (train.py:196: 3; 0 = fp32)')
@@ -600,7 +605,7 @@ def main():
     ap.add_argument('--mode', choices=['synthesis', 'generator', 'generator_routed', 'train', 'bf16_1024', 'selftest'], default='synthesis',
                     help="'synthesis' = the headline (config 2); 'generator' = config 3 (encoders + mapping + synthesis, N=16) on synthetic tensors, 'generator_routed' = the same behind the HIP patch routing of every sample; 'train' = config 4 step; "
                          "'bf16_1024' = config 5 (StyleGAN2 stack at 1024^2 in bf16, N=4); 'selftest' = launcher / rank plumbing on CPU over gloo with a stub forward (no measurement)")
-    ap.add_argument('--no-secondary', action='store_true', help='headline mode: skip the config 3 / config 5 child runs')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full, headline mode: skip the config 3 / 5 / 4 child runs')
     ap.add_argument('--channel-max', type=int, default=1024, help="config 5: widest layer (SURVEY 8d: 'channels 1024 -> 32')")
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='headline mode: write the outputs of the last timed step (img, finetune_img, pred_parsing of rank 0) as DIR/<name>.npy, '
@@ -687,11 +692,11 @@ def main():
                     roofline=roofline)
         if args.dump_outputs:                                  # `out` is the last timed step's result; nothing has run on the GPU since
             line['dumped_outputs'] = dict(dir=args.dump_outputs, arrays=dump_outputs(dict(zip(('img', 'finetune_img', 'pred_parsing'), out)), args.dump_outputs))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline()
-        if world == 1 and not args.no_secondary and under_profiler():
+        if args.full and world == 1 and not args.no_secondary and under_profiler():
             line['secondary'] = dict(skipped='a profiler tool library is preloaded into this process')
-        elif world == 1 and not args.no_secondary:
+        elif args.full and world == 1 and not args.no_secondary:
             del net, inp, out                                  # the children get the whole GPU
             torch.cuda.empty_cache()
             line['secondary'] = secondary_runs()

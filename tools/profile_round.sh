@@ -14,7 +14,8 @@ rm -f gpurun_out/pmc/summary.txt
 bash tools/pmc_run.sh > gpurun_out/pmc_wino.log 2>&1
 bash tools/pmc16_run.sh 4 64 64 512 > gpurun_out/pmc16.log 2>&1
 cd $R
-python bench.py > gpurun_out/bench_cfg2.json 2> gpurun_out/bench_cfg2.err
-python bench.py --mode bf16_1024 > gpurun_out/bench_cfg5.json 2> gpurun_out/bench_cfg5.err
+OUT=$(python3 -c 'import sys; sys.path.insert(0, "tools"); import collect_profiles; print(collect_profiles.G)')   # the folder tools/collect_profiles.py reads
+python bench.py --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+python bench.py --mode bf16_1024 --full > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
 python bench.py --mode train --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/bench_train.json 2> gpurun_out/bench_train.err
 tail -1 gpurun_out/bench_cfg2.json | cut -c1-400; tail -1 gpurun_out/bench_cfg5.json | cut -c1-400; tail -1 gpurun_out/bench_train.json | cut -c1-400
