@@ -2,7 +2,8 @@
  * pasta_gan_ops.h -- C ABI of the MI355X (gfx950) kernels behind PASTA-GAN++'s
  * generator-synthesis operator API.
  *
- * Seven shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing, the augment pipe and the try-on staging):
+ * Eight shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing, the augment pipe, the try-on staging
+ * and the training loop's data fetch):
  *   bias_act_plugin.so      pg_bias_act
  *   upfirdn2d_plugin.so     pg_upfirdn2d, pg_upfirdn2d_bias_act, pg_upfirdn2d_with_odd_samples
  *   conv2d_plugin.so        fp32: pg_conv2d_{packed_size,pack_weight,forward,splitk_plan,forward_splitk}, pg_conv2d_winograd_*,
@@ -12,6 +13,7 @@
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
  *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color
  *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8
+ *   train_fetch_plugin.so   pg_train_fetch
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -647,6 +649,44 @@ int pg_tryon_inputs(const pg_tryon_io* io, int n, int H, int W, int h, int w, in
 int pg_tryon_triptych_u8(const float* finetune_img, const unsigned char* clothes, const unsigned char* image, unsigned char* out, int n, int H, int W,
                          int x0, int cw, void* stream);
 int pg_tryon_abi_version(void);
+
+/* train_fetch_plugin.so -- the data fetch of the training loop (training/train_fetch.py; reference training_loop_fullbody.py:549-601 and the tail of
+ * its loader, training/dataset.py:1146-1170, :1223-1241).  Results equal torch's GPU arithmetic bit for bit, as for tryon_plugin.so.
+ * pg_train_fetch: the nine float32 NCHW tensors of a round for a batch of n, in one launch.  Sources are uint8 NHWC (H x W canvases, h x w part
+ *   patches; W, w multiples of 4; dword-aligned), outputs dense float32 NCHW (16-byte aligned).  Per sample i the erase decision erase[i] =
+ *   (kind, rows flag, erase_length, use_random_mask) is applied while reading, unless extents[i, 0] < 0 (the routed lower mask of part 0 is empty):
+ *   PG_ERASE_DROP_PART0 zeroes channels 0..2 of norm_img_lower and, with the rows flag, rows 0 : erase_length of channels 3..5 and 9..11;
+ *   PG_ERASE_BAND zeroes rows ty : by of channels 0..2, ty = extents[i, 0], by = min(ty + 1 + floor(band_u[i] * (h - ty)), h) in float32.
+ *   With use_random_mask (and random_mask != NULL) the canvases are zeroed where random_mask > 0 before the masks are taken. */
+enum pg_erase_kind { PG_ERASE_NONE = 0, PG_ERASE_DROP_PART0 = 1, PG_ERASE_BAND = 2 };
+typedef struct pg_train_io {
+    const unsigned char* image;            /* [n, H, W, 3] */
+    const unsigned char* pose;             /* [n, H, W, 3] */
+    const unsigned char* retain_mask;      /* [n, H, W, 1]: 0 / 1 */
+    const unsigned char* gt_parsing;       /* [n, H, W, 1]: 0 .. 6 */
+    const unsigned char* random_mask;      /* [n, H, W, 1] or NULL */
+    const unsigned char* denorm_upper;     /* [n, H, W, 3] */
+    const unsigned char* denorm_lower;     /* [n, H, W, 3] */
+    const unsigned char* norm_img;         /* [n, h, w, 30] */
+    const unsigned char* norm_img_lower;   /* [n, h, w, 15], before the erase */
+    const float* skin;                     /* [n, 3]: the skin medians (float32, NaN kept) */
+    const int* label;                      /* [n]: 0, 1 or 2 */
+    const unsigned char* bound_rows;       /* [n, H]: lower_clothes_upper_bound_for_train, one value per row */
+    const int* extents;                    /* [n, 2] from pg_tryon_row_extent_u8 over the routed lower mask of part 0 ([n, h, w, 3]) */
+    const int* erase;                      /* [n, 4]: kind (pg_erase_kind), rows flag, erase_length, use_random_mask */
+    const float* band_u;                   /* [n]: u in [0, 1) of PG_ERASE_BAND */
+    float* real_img;                       /* [n, 3, H, W] */
+    float* style_input;                    /* [n, 45, h, w] */
+    float* retain;                         /* [n, 6, H, W] */
+    float* pose_out;                       /* [n, 5, H, W] */
+    float* denorm_upper_out;               /* [n, 3, H, W] */
+    float* denorm_lower_out;               /* [n, 3, H, W] */
+    float* upper_mask_out;                 /* [n, 1, H, W] */
+    float* lower_mask_out;                 /* [n, 1, H, W] */
+    float* gt_parsing_out;                 /* [n, 1, H, W] */
+} pg_train_io;
+int pg_train_fetch(const pg_train_io* io, int n, int H, int W, int h, int w, void* stream);
+int pg_train_fetch_abi_version(void);
 
 #ifdef __cplusplus
 }

@@ -7,30 +7,14 @@
 // reciprocal 1.0f / 127.5f (tests/test_tryon_gpu.py pins this over all 256 byte values), so `unit` does the same.
 // Memory-bound streams: one lane = 4 consecutive pixels of a row -> 16-byte float4 stores per plane; the uint8 sides are read as dwords.
 #include "pg_common.h"
+#include "pg_stage.h"
 #include <cstdint>
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kInv = 1.0f / 127.5f;            // what torch multiplies by for `t / 127.5` on a GPU tensor
-
-__device__ __forceinline__ float unit(float u) { return u * kInv - 1.0f; }
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
-
-template <int C>
-__device__ __forceinline__ void load_px4(const uint8_t* __restrict__ p, uint32_t (&w)[C]) {      // 4 pixels x C bytes, dword aligned
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-    for (int i = 0; i < C; i++) w[i] = __builtin_nontemporal_load(q + i);
-}
-
-__device__ __forceinline__ void store4(float* __restrict__ p, float a, float b, float c, float d) {
-    __builtin_nontemporal_store(f32x4{a, b, c, d}, reinterpret_cast<f32x4*>(p));
-}
+using namespace pg::stage;       // f32x4, u32x4, unit, byte_of, load_px4, store4 (shared with csrc/train_fetch.hip)
 
 // ----------------------------------------------------------------------------------------------------------- row extents
 // One workgroup per canvas: every lane scans 16-byte chunks (a chunk never straddles a row: row_bytes % 16 == 0) and keeps its own first / last

@@ -1,4 +1,7 @@
-"""Test-time loader of try-on pairs (BASELINE config 1): the reference's three test sets, chosen by ``part=`` as test.py's
+"""The loaders.  `TrainSet` (at the end of the module) is the training set, the reference's ``UvitonDatasetFull_512`` (training/dataset.py:404-1248);
+the rest of this docstring is about the test-time loader.
+
+Test-time loader of try-on pairs (BASELINE config 1): the reference's three test sets, chosen by ``part=`` as test.py's
 ``--testpart`` chooses them -- 'upper' ``UvitonDatasetFull_512_test_upper`` (training/dataset.py:1952-2728), 'lower'
 ``UvitonDatasetFull_512_test_lower`` (:2729-3456), 'full' ``UvitonDatasetFull_512_test_full`` (:1251-1951).  Reads the reference's
 file formats and produces the 16-tuple every one of them returns (:2702-2726, :3456-3482, :1925-1950) -- uint8 CHW arrays
@@ -20,8 +23,10 @@ quadrilaterals, square dilation) with its own pixel-coverage rules, so those two
 reference's libraries (shapes, dtypes, value sets and topology are; DESIGN.md says so).
 """
 
+import collections
 import json
 import os
+import random
 
 import numpy as np
 import torch
@@ -157,8 +162,8 @@ class TryOnTestSet(torch.utils.data.Dataset):
     def __init__(self, path, test_txt='test_pairs.txt', use_sleeve_mask=False, device='cpu', part='upper'):
         if PIL is None:
             raise ImportError('TryOnTestSet needs Pillow')
-        if part not in patch_routing.MODES:
-            raise ValueError(f'part must be one of {sorted(patch_routing.MODES)}, not {part!r}')
+        if part not in patch_routing.TRYON_MODES:
+            raise ValueError(f'part must be one of {sorted(patch_routing.TRYON_MODES)}, not {part!r}')
         self.path, self.use_sleeve_mask, self.device, self.part = path, use_sleeve_mask, device, part
         self.pairs = []
         with open(os.path.join(path, test_txt)) as f:
@@ -456,5 +461,245 @@ def collate_unrouted(items, pin=False):
     label = torch.tensor([it['label'] for it in items], dtype=torch.int32)
     out['skin'], out['label'] = (skin.pin_memory(), label.pin_memory()) if pin else (skin, label)
     for k in ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'):
+        out[k] = [it[k] for it in items]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- the training set
+
+DATASET_LIST = ['Zalando_512_320_v1', 'Zalando_512_320_v2', 'Zalora_512_320_v1', 'Zalora_512_320_v2', 'Deepfashion_512_320', 'MPV_512_320',
+                'ZMO_dresses_512_320', 'Zalando_512_320_v1_flip', 'Zalando_512_320_v2_flip', 'Zalora_512_320_v1_flip', 'Zalora_512_320_v2_flip',
+                'Deepfashion_512_320_flip', 'MPV_512_320_flip', 'ZMO_dresses_512_320_flip']                  # dataset.py:415-421
+TRAIN_LIST = 'train_pairs_front_list_220508.txt'
+ERASE_NONE, ERASE_DROP_PART0, ERASE_BAND = 0, 1, 2            # enum pg_erase_kind (include/pasta_gan_ops.h)
+
+# The random decisions of one training item (dataset.py:1160-1170, :1226), drawn on the host and applied where the routed patches are:
+# kind: ERASE_*; rows: with ERASE_DROP_PART0, also erase the top `erase_length` rows of lower parts 1 and 3; u in [0, 1): with ERASE_BAND, rows
+# ty : ty + 1 + floor(u * (h - ty)) of lower part 0 (ty = first row of its routed mask); use_random_mask: erase the canvases under the item's random mask.
+EraseRecord = collections.namedtuple('EraseRecord', 'kind rows erase_length u use_random_mask')
+NO_ERASE = EraseRecord(ERASE_NONE, 0, 0, 0.0, 0)
+
+
+def sample_record(rng, h=SIDE // 4):
+    """One `EraseRecord` from `rng` (a ``random.Random``), with the reference's probabilities: none 0.20, drop_part0 0.8 * 0.6 = 0.48 (its row erase
+    0.75, erase_length uniform on 1 ... h // 10), band 0.8 * 0.4 = 0.32; random mask 0.9.  The reference draws from the global ``random`` and only if
+    the routed lower mask is non-empty; this draws every field's decision up front, so its stream is not the reference's."""
+    kind, rows, erase_length, u = ERASE_NONE, 0, 0, 0.0
+    if rng.random() < 0.80:
+        if rng.random() < 0.6:
+            kind = ERASE_DROP_PART0
+            if rng.random() < 0.75:
+                rows, erase_length = 1, rng.randint(1, h // 10)
+        else:
+            kind, u = ERASE_BAND, float(np.float32(rng.random()))
+            if u >= 1.0:                                      # (the float32 rounding of a draw within 2**-25 of 1)
+                u = float(np.nextafter(np.float32(1), np.float32(0)))
+    return EraseRecord(kind, rows, erase_length, u, int(rng.random() < 0.9))
+
+
+def apply_erase(norm_img_lower, masks_lower, record):
+    """``norm_img_lower_for_train`` (dataset.py:1146-1170) of a routed [h, w, 15] uint8 array and its routed masks, for a given record (NumPy)."""
+    out = norm_img_lower.copy()
+    bbox = _bbox(masks_lower[..., 0:1].copy())
+    if bbox is None or record.kind == ERASE_NONE:
+        return out
+    h = out.shape[0]
+    if record.kind == ERASE_DROP_PART0:
+        out[..., 0:3] = 0
+        if record.rows:
+            out[0:record.erase_length, :, 3:6] = 0
+            out[0:record.erase_length, :, 9:12] = 0
+    else:
+        ty = bbox[1]
+        by = min(ty + 1 + int(np.floor(np.float32(record.u) * np.float32(h - ty))), h)
+        out[ty:by, :, 0:3] = 0
+    return out
+
+
+class TrainSet(torch.utils.data.Dataset):
+    """The reference's training set ``UvitonDatasetFull_512`` (dataset.py:404-1248) for its directory layout: ``<path>/<dataset>/{image,keypoints,
+    parsing,garment_parsing}/...`` listed by ``<path>/<dataset>/train_pairs_front_list_220508.txt`` (first column; ``_label.png`` parsing names for
+    Deepfashion_512_320 and MPV_512_320) and ``<path>/train_random_mask_acgpn/*``.  Sub-datasets of `dataset_list` that are absent are skipped;
+    ``train_img_front_vis_512_220414`` is optional (`vis_index` is empty without it).  One person per item, routed through their own key points.
+
+    ``ds[idx]`` is the reference's 19-tuple (:1198-1248), routed on `device` ('cpu' = the NumPy route):
+
+        image[3,512,512] pose[3,512,512] norm_img[30,128,128] norm_img_lower[15,128,128] norm_img_lower_for_train[15,128,128]
+        denorm_upper_img_erase[3,512,512] denorm_lower_img_erase[3,512,512] Ms[10,3,3] M_invs[10,3,3] gt_parsing[1,512,512]
+        denorm_upper_mask[1,512,512] denorm_lower_mask[1,512,512] norm_clothes_masks[30,128,128] norm_clothes_masks_lower[15,128,128]
+        retain_mask[1,512,512] skin_median[3,512,512] lower_label_map[1,512,512] lower_clothes_upper_bound_for_train[1,512,512] ..._for_test[1,512,512]
+
+    (uint8, except Ms / M_invs / skin_median / lower_label_map: float64).  ``ds.unrouted(idx)`` is what the host makes before the routing, for the
+    batched GPU route (training/train_fetch.py).  The random decisions come from `sample_record` on a ``random.Random`` seeded by (seed, DataLoader
+    worker, index, how often this worker has drawn for the index): reproducible, not the reference's draw-for-draw stream."""
+
+    def __init__(self, path, dataset_list=None, shuffle=True, seed=0, device='cpu'):
+        if PIL is None:
+            raise ImportError('TrainSet needs Pillow')
+        if not os.path.isdir(path):
+            raise IOError('Path must point to a directory')
+        self.path, self.device, self.seed = path, device, seed
+        names = []                                            # (image, keypoints, parsing, garment_parsing), relative to path
+        for dataset in (DATASET_LIST if dataset_list is None else dataset_list):
+            txt = os.path.join(path, dataset, TRAIN_LIST)
+            if not os.path.isfile(txt):
+                continue
+            label_suffix = '_label.png' if dataset in ('Deepfashion_512_320', 'MPV_512_320') else '.png'
+            with open(txt) as f:
+                for line in f:
+                    if not line.strip():
+                        continue
+                    person = line.strip().split()[0]
+                    names.append((os.path.join(dataset, 'image', person), os.path.join(dataset, 'keypoints', person.replace('.jpg', '_keypoints.json')),
+                                  os.path.join(dataset, 'parsing', person.replace('.jpg', label_suffix)),
+                                  os.path.join(dataset, 'garment_parsing', person.replace('.jpg', '.png'))))
+        if not names:
+            raise IOError('No image files found in the specified path')
+        if shuffle:
+            random.Random(seed).shuffle(names)
+        self.names = names
+        images = [n[0] for n in names]
+        self.vis_index = []
+        vis_dir = os.path.join(path, 'train_img_front_vis_512_220414')
+        if os.path.isdir(vis_dir):                            # dataset.py:447-461
+            for image_name in sorted(os.listdir(vis_dir)):
+                for cand in (os.path.join('Zalando_512_320_v1', 'image', image_name), os.path.join('Deepfashion_512_320', 'image', 'train', image_name),
+                             os.path.join('Zalora_512_320_v2', 'image', image_name)):
+                    if cand in images:
+                        self.vis_index.append(images.index(cand))
+                        break
+        mask_dir = os.path.join(path, 'train_random_mask_acgpn')
+        self.random_masks = [os.path.join(mask_dir, m) for m in sorted(os.listdir(mask_dir))] if os.path.isdir(mask_dir) else []
+        if not self.random_masks:
+            raise IOError('no random masks in ' + mask_dir)
+        self._visits = collections.Counter()
+
+    pose_map = staticmethod(TryOnTestSet.pose_map)            # the drawing statements agree with the training class (:698-823)
+    _limb_band = staticmethod(TryOnTestSet._limb_band)
+    _arm_masks = TryOnTestSet._arm_masks
+    palm_mask = TryOnTestSet.palm_mask
+
+    def __len__(self):
+        return len(self.names)
+
+    def record(self, idx):
+        """The next `EraseRecord` of item `idx` in this process."""
+        info = torch.utils.data.get_worker_info()
+        visit = self._visits[idx]
+        self._visits[idx] += 1
+        return sample_record(random.Random(f'{self.seed}/{0 if info is None else info.id}/{int(idx)}/{visit}'))
+
+    def _labels(self, name):
+        a = np.array(PIL.Image.open(os.path.join(self.path, name)))
+        return (a if a.ndim == 2 else a[..., 0])[..., None]
+
+    def _random_mask(self, idx):
+        a = np.array(PIL.Image.open(self.random_masks[idx % len(self.random_masks)]))
+        return np.ascontiguousarray((a if a.ndim == 2 else a[..., 0])[..., None])
+
+    def _host(self, idx):
+        """``_load_raw_image`` up to the routing (dataset.py:507-632, :644-651)."""
+        image_name, kpt_name, parsing_name, garment_name = self.names[idx]
+        raw = np.array(PIL.Image.open(os.path.join(self.path, image_name)).convert('RGB'))
+        assert raw.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
+        image, left = _pad_square(raw, 255)
+        with open(os.path.join(self.path, kpt_name)) as f:
+            people = json.load(f)['people']
+        kp = np.array(people[0]['pose_keypoints_2d'], dtype=np.float64).reshape(-1, 3) if people else np.zeros((18, 3))
+        pose, kp = self.pose_map(kp, raw.shape[:2])
+        pose, _ = _pad_square(pose, 0)
+        kp[:, 0] += left
+        garment_parsing, _ = _pad_square(self._labels(garment_name), 0)
+        sleeve = np.isin(garment_parsing, (10, 11)).astype(np.uint8)
+        parsing, _ = _pad_square(self._labels(parsing_name), 0)
+
+        is_ = lambda *labels: np.isin(parsing, labels).astype(np.uint8)
+        retain_mask = is_(18, 19) + self.palm_mask(kp, parsing) + is_(1, 2, 4, 13)             # shoes + palms + head
+        hand_leg, neck = is_(14, 15, 16, 17), is_(10)
+        skin = is_(10, 13) * image
+        medians = []
+        for ch in range(3):
+            vals = skin[..., ch].reshape(-1)
+            vals = vals[vals > 0]
+            medians.append(np.median(vals) if vals.size else np.nan)
+        tops, dresses, pants, skirt = _garment_classes(parsing)               # dataset.py:568-594: the same statements as the test classes'
+        gt_parsing = tops * 1 + pants * 2 + skirt * 3 + dresses * 4 + neck * 5 + hand_leg * 6
+        lower_mask, upper_mask = skirt + pants, tops + dresses
+        upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
+
+        lower_bbox = _bbox(lower_mask.copy())
+        bound_train = np.zeros(SIDE, dtype=np.uint8)          # one value per row: the maps are constant along each row
+        if lower_bbox is not None:
+            bound_train[lower_bbox[1]:] += 255
+        bound_test = np.zeros(SIDE, dtype=np.uint8)
+        lhip, rhip = kp[11], kp[8]
+        if lhip[2] > 0.05 and rhip[2] > 0.05:
+            via_kps = int((lhip[1] + rhip[1]) / 2 - np.linalg.norm(lhip[0:2] - rhip[0:2]) / 2)
+            top = via_kps if lower_bbox is None else min(lower_bbox[1], via_kps)
+            bound_test[top:] += 255                           # (NumPy slice semantics, negative values included, as in the reference)
+        elif lower_bbox is not None:
+            bound_test[lower_bbox[1]:] += 255
+        label = 0 if pants.sum() > 0 else (1 if skirt.sum() > 0 else (2 if dresses.sum() > 0 else 1))
+        return dict(upper_img=(upper_mask * image).astype(np.uint8), lower_img=(lower_mask * image).astype(np.uint8), upper_mask=upper_rgb.astype(np.uint8),
+                    lower_mask=lower_rgb.astype(np.uint8), sleeve=sleeve, person_kp=kp, image=image, pose=pose, gt_parsing=gt_parsing.astype(np.uint8),
+                    retain_mask=retain_mask, skin=np.array(medians, dtype=np.float64), label=label, bound_train=bound_train, bound_test=bound_test,
+                    name=image_name)
+
+    def unrouted(self, idx, record=None):
+        """Everything the host makes of item `idx`, before the routing: a dict of
+
+        upper_img, lower_img, upper_mask, lower_mask   uint8 [512, 512, 3]: the routing inputs of ``patch_routing.normalize_batch(part='train')``
+        sleeve                                         uint8 [512, 512, 1]; person_kp float64 [18, 3]
+        image, pose                                    uint8 [512, 512, 3] (HWC); gt_parsing, retain_mask uint8 [512, 512, 1]
+        skin                                           float64 [3]: the skin medians, NaN kept; label int: 0, 1 or 2
+        bound_train, bound_test                        uint8 [512]: the two bound maps, one value per row
+        random_mask                                    uint8 [512, 512, 1], or None when the record does not use it
+        record                                         the `EraseRecord` (drawn with ``self.record(idx)`` unless given); name"""
+        item = self._host(idx)
+        item['record'] = rec = self.record(idx) if record is None else record
+        item['random_mask'] = self._random_mask(idx) if rec.use_random_mask else None
+        return item
+
+    def __getitem__(self, idx):
+        return self.item(idx)
+
+    def item(self, idx, record=None):
+        """The 19-tuple of item `idx` under `record` (drawn unless given)."""
+        u = self.unrouted(idx, record)
+        routed = patch_routing.normalize(u['upper_img'], u['lower_img'], u['upper_mask'], u['lower_mask'], u['sleeve'], u['person_kp'], u['person_kp'], 2,
+                                         device=self.device, part='train')
+        norm_img, norm_img_lower, denorm_upper, denorm_lower, masks, masks_lower = (t.cpu().numpy() for t in routed)
+        for_train = apply_erase(norm_img_lower, masks_lower, u['record'])
+        ms, m_invs = patch_routing.crop_matrices(u['person_kp'], SIDE, SIDE, 2)
+        chw = lambda a: np.ascontiguousarray(np.transpose(a, (2, 0, 1)))
+        random_mask = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)
+        if u['random_mask'] is not None:                      # dataset.py:1223-1241
+            random_mask += u['random_mask']
+        keep = 1 - chw((random_mask > 0).astype(np.uint8))
+        upper_erase, lower_erase = chw(denorm_upper) * keep, chw(denorm_lower) * keep
+        rows = lambda b: np.ascontiguousarray(np.broadcast_to(b[None, :, None], (1, SIDE, SIDE)))
+        return (chw(u['image']), chw(u['pose']), chw(norm_img), chw(norm_img_lower), chw(for_train), upper_erase, lower_erase, ms, m_invs,
+                chw(u['gt_parsing']), (np.sum(upper_erase, axis=0, keepdims=True) > 0).astype(np.uint8),
+                (np.sum(lower_erase, axis=0, keepdims=True) > 0).astype(np.uint8), chw(masks), chw(masks_lower), chw(u['retain_mask']),
+                chw(TryOnTestSet._skin_map(u['skin'])), np.full((1, SIDE, SIDE), u['label'] / 2.0 * 255), rows(u['bound_train']), rows(u['bound_test']))
+
+
+_TRAIN_ARRAYS = ('upper_img', 'lower_img', 'upper_mask', 'lower_mask', 'sleeve', 'image', 'pose', 'gt_parsing', 'retain_mask', 'bound_train', 'bound_test')
+
+
+def collate_train(items, pin=False):
+    """Stack ``TrainSet.unrouted`` items into a batch: the uint8 arrays as [N, ...] tensors (pinned with pin=True, as `collate_unrouted`), skin as
+    float32 [N, 3] (NaN kept), label int32 [N], random_mask uint8 [N, 512, 512, 1] (zeros for an item without one), the records as `erase` int32
+    [N, 4] = (kind, rows, erase_length, use_random_mask) and `band_u` float32 [N]; key points, records and names stay lists."""
+    out = {k: torch.from_numpy(np.stack([it[k] for it in items])) for k in _TRAIN_ARRAYS}
+    zero = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)
+    out['random_mask'] = torch.from_numpy(np.stack([zero if it['random_mask'] is None else it['random_mask'] for it in items]))
+    out['skin'] = torch.from_numpy(np.stack([it['skin'] for it in items])).to(torch.float32)
+    out['label'] = torch.tensor([it['label'] for it in items], dtype=torch.int32)
+    out['erase'] = torch.tensor([[r.kind, r.rows, r.erase_length, r.use_random_mask] for r in (it['record'] for it in items)], dtype=torch.int32)
+    out['band_u'] = torch.tensor([it['record'].u for it in items], dtype=torch.float32)
+    if pin:
+        out = {k: v.pin_memory() for k, v in out.items()}
+    for k in ('person_kp', 'record', 'name'):
         out[k] = [it[k] for it in items]
     return out

@@ -20,10 +20,14 @@ part      upper-garment warp        lower-garment warp        erode   lower part
 upper     clothes crop (:2605)      person crop (:2634)       8 x 8   torso / hips (:2654-2663)    5 (+ denorm_upper_img_wo_sleeve)
 lower     person crop (:3361)       clothes crop (:3388)      5 x 5   torso / hips (:3408-3417)    4
 full      clothes crop (:1843)      clothes crop (:1869)      5 x 5   no                           4
+train     person crop (:1063)       person crop (:1077)       5 x 5   no                           6 (+ the routed clothes masks)
 ========  ========================  ========================  ======  ===========================  ==========================
 
-(upper: dataset.py:2555-2700 ``UvitonDatasetFull_512_test_upper.normalize``; lower: :3313-3454; full: :1796-1923.)  Every
-de-normalising warp uses the person crop's inverse; the missing-sleeve mirroring is the same in all three.
+(upper: dataset.py:2555-2700 ``UvitonDatasetFull_512_test_upper.normalize``; lower: :3313-3454; full: :1796-1923; train: :1010-1195
+``UvitonDatasetFull_512.normalize``.)  Every de-normalising warp uses the person crop's inverse; the missing-sleeve mirroring is the same in all
+four.  The training mode routes a person through their own key points (self-reconstruction): there is one crop set, computed once; the sleeve
+mask is always applied; and the routed clothes masks (mirrored like the images) are results too.  Its random erase of the lower-garment patches is
+not part of the routing: the loader draws a decision record and training.train_fetch applies it.
 """
 
 import ctypes
@@ -42,7 +46,9 @@ SLEEVE_PARTS = (2, 3, 4, 5)
 _J = {name: i for i, name in enumerate(ORDER)}
 # part -> (upper garment warped with the clothes crop?, lower garment warped with the clothes crop?, erode window, lower parts give way to the upper
 # garment?, denorm_upper_img_wo_sleeve returned?)
-MODES = {'upper': (True, False, 8, True, True), 'lower': (False, True, 5, True, False), 'full': (True, True, 5, False, False)}
+MODES = {'upper': (True, False, 8, True, True), 'lower': (False, True, 5, True, False), 'full': (True, True, 5, False, False),
+         'train': (False, False, 5, False, False)}
+TRYON_MODES = ('upper', 'lower', 'full')     # test.py --testpart; 'train' is the training loader's mode (one crop set, masks returned)
 
 
 def _mode(part):
@@ -188,6 +194,18 @@ def get_crop(keypoints, bpart, wh, o_w, o_h, ar=1.0, _quad_only=False):
         return quad
     part_dst = np.float32(wh * np.float32([[0.0, 0.0], [0.0, 1.0], [1.0, 1.0], [1.0, 0.0]]))
     return get_perspective_transform(quad, part_dst), get_perspective_transform(part_dst, quad)
+
+
+def crop_matrices(keypoints, o_h, o_w, box_factor):
+    """``Ms`` / ``M_invs`` [10, 3, 3] float64 of the training loader (dataset.py:1087-1091, :1191-1192): `get_crop` of the ten parts, zeros for a
+    missing part."""
+    wh = np.expand_dims(np.array([o_w // 2 ** box_factor, o_h // 2 ** box_factor]), 0)
+    ms, m_invs = np.zeros((10, 3, 3)), np.zeros((10, 3, 3))
+    for ii, bpart in enumerate(BPARTS):
+        m, m_inv = get_crop(keypoints, bpart, wh, o_w, o_h, 0.5 if ii < 6 else 0.4)
+        if m is not None:
+            ms[ii], m_invs[ii] = m, m_inv
+    return ms, m_invs
 
 
 def perspective_transforms(src, dst):
@@ -369,9 +387,14 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
 
     part='upper' (dataset.py:2555-2700): (img [h,w,30], img_lower [h,w,15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img)
     part='lower' (:3313-3454) and part='full' (:1796-1923): (img [h,w,30], img_lower [h,w,15], denorm_upper_img, denorm_lower_img)
+    part='train' (:1010-1195): (img, img_lower, denorm_upper_img, denorm_lower_img, clothes_masks [h,w,30], clothes_masks_lower [h,w,15]);
+        `clothes_keypoints` is not read (the person is routed through `person_keypoints`), `sleeve_mask` is required
 
     (h, w = H / 2**box_factor, W / 2**box_factor; the canvases are [H, W, 3].)"""
     up_by_clothes, lo_by_clothes, ksize, lower_minus_upper, wo_sleeve = _mode(part)
+    train = part == 'train'
+    if train and sleeve_mask is None:
+        raise ValueError("patch_routing: part='train' needs the sleeve mask (dataset.py:1063-1067 applies it unconditionally)")
     dev = torch.device(device)
     up, lo = _gpu_u8(upper_img, dev), _gpu_u8(lower_img, dev)
     um, lm = _gpu_u8(upper_clothes_mask, dev), _gpu_u8(lower_clothes_mask, dev)
@@ -387,7 +410,8 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
     crops = []
     for ii, bpart in enumerate(BPARTS):
         ar = 0.5 if ii < 6 else 0.4
-        crops.append((get_crop(clothes_keypoints, bpart, wh, o_w, o_h, ar), get_crop(person_keypoints, bpart, wh, o_w, o_h, ar)))
+        person_crop = get_crop(person_keypoints, bpart, wh, o_w, o_h, ar)
+        crops.append((person_crop if train else get_crop(clothes_keypoints, bpart, wh, o_w, o_h, ar), person_crop))
 
     # stage 1: image -> patch (the upper / lower garment through the clothes' or the person's crop, as the mode says)
     up_m = [c[0][0] if up_by_clothes else c[1][0] for c in crops]
@@ -453,6 +477,9 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
 
     if wo_sleeve:
         return torch.cat(part_imgs, dim=2), torch.cat(part_imgs_lower, dim=2), denorm_upper, denorm_upper_wo_sleeve, denorm_lower
+    if train:
+        return (torch.cat(part_imgs, dim=2), torch.cat(part_imgs_lower, dim=2), denorm_upper, denorm_lower, torch.cat(part_masks, dim=2),
+                torch.cat(part_masks_lower, dim=2))
     return torch.cat(part_imgs, dim=2), torch.cat(part_imgs_lower, dim=2), denorm_upper, denorm_lower
 
 
@@ -469,9 +496,13 @@ def normalize_batch(samples, box_factor, device='cuda', part='upper'):
     samples: list of (upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, sleeve_mask | None, clothes_keypoints, person_keypoints), images uint8
     [H, W, 3] (all the same size).  Returns the results of `normalize(..., part=part)`, stacked -- part='upper': img [N, h, w, 30], img_lower
     [N, h, w, 15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img [N, H, W, 3]; part='lower' / 'full': the same without
-    denorm_upper_img_wo_sleeve -- bit-identical to the per-sample calls (tests/test_patch_routing.py, tests/test_routing_modes_gpu.py).  Every mode is the
-    same three launches; the mode only picks which crop warps which garment, the erode window and the masking of the lower parts."""
+    denorm_upper_img_wo_sleeve; part='train': those four plus clothes_masks [N, h, w, 30] and clothes_masks_lower [N, h, w, 15] -- bit-identical to the
+    per-sample calls (tests/test_patch_routing.py, tests/test_routing_modes_gpu.py, tests/test_train_fetch_gpu.py).  Every mode is the same three
+    launches; the mode only picks which crop warps which garment, the erode window, the masking of the lower parts and what is returned."""
     up_by_clothes, lo_by_clothes, ksize, lower_minus_upper, wo_sleeve = _mode(part)
+    train = part == 'train'
+    if train and any(s[4] is None for s in samples):
+        raise ValueError("patch_routing: part='train' needs the sleeve mask of every sample")
     dev = torch.device(device)
     n = len(samples)
     if dev.type != 'cuda':
@@ -503,7 +534,7 @@ def normalize_batch(samples, box_factor, device='cuda', part='upper'):
     for i, s in enumerate(samples):
         for ii, bpart in enumerate(BPARTS):
             ar = 0.5 if ii < 6 else 0.4
-            for store, kp in ((cq, s[5]), (pq, s[6])):
+            for store, kp in ((pq, s[6]),) if train else ((cq, s[5]), (pq, s[6])):      # (train: clothes and person are one crop set, computed once)
                 q = get_crop(kp, bpart, wh, o_w, o_h, ar, _quad_only=True)
                 if not isinstance(q, tuple):
                     store[(i, ii)] = q
@@ -601,4 +632,9 @@ def normalize_batch(samples, box_factor, device='cuda', part='upper'):
     img_lower = imgs_lo.permute(0, 2, 3, 1, 4).reshape(n, h, w, 15)
     if wo_sleeve:
         return img, img_lower, D[0], D[1], D[2]
+    if train:                       # the routed clothes masks, mirrored as written (:1105-1129): every branch mirrors the other side's mask
+        new_masks = torch.stack([masks[:, 0], masks[:, 1], torch.where(c24, flip(m4), m2), torch.where(c35, flip(m5), m3), torch.where(c42, flip(m2), m4),
+                                 torch.where(c53, flip(m3), m5), masks[:, 6], masks[:, 7], masks[:, 8], masks[:, 9]], dim=1)
+        return (img, img_lower, D[0], D[1], new_masks.permute(0, 2, 3, 1, 4).reshape(n, h, w, 30),
+                P1[:, 25:30].permute(0, 2, 3, 1, 4).reshape(n, h, w, 15))
     return img, img_lower, D[0], D[1]
