@@ -596,7 +596,34 @@ typedef struct pg_compose_job {
 } pg_compose_job;
 int pg_patch_compose_ordered_u8(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, void* stream);
 int pg_patch_compose_ordered_u8_k(const pg_compose_job* jobs_device, int njobs, int h, int w, int mask_channels, int ksize, void* stream);
+/* The fused de-normalisation of the snapshot grid (training/snapshot_grid.py): ph x pw patches -> H x W canvas in one launch, without the warped
+ * intermediates.  job = one H x W x 3 canvas and up to PG_COMPOSE_MAX_PARTS parts in paste order, each a ph x pw x 3 patch, a ph x pw x mask_channels mask
+ * (channel 0 is used) and `minv` (as pg_warp_job's).  Every canvas pixel is written: the patch of the LAST part whose eroded warped mask is 255 there, warped;
+ * 0 where there is none.  The result equals, byte for byte, pg_warp_perspective_u8 of every patch and mask to H x W with the same `block_w` followed by
+ * pg_patch_compose_ordered_u8_k with the same `ksize` (1..16, anchor ksize / 2, taps outside the canvas ignored).  `jobs_device` lives in device memory.
+ * PG_ERR_INVALID_ARG: NULL table, a non-positive size, ksize outside 1..16. */
+typedef struct pg_denorm_job {
+    unsigned char* canvas;
+    const unsigned char* patch[PG_COMPOSE_MAX_PARTS];
+    const unsigned char* mask[PG_COMPOSE_MAX_PARTS];
+    double minv[PG_COMPOSE_MAX_PARTS][9];
+    int nparts;
+    int pad_;
+} pg_denorm_job;
+int pg_patch_denorm_u8(const pg_denorm_job* jobs_device, int njobs, int H, int W, int ph, int pw, int mask_channels, int ksize, int block_w, void* stream);
 int pg_patch_routing_abi_version(void);
+
+/* snapshot_grid_plugin.so -- the image snapshots of the training driver (training/snapshot_grid.py; the reference's save_image_grid,
+ * training_loop_fullbody.py:313-340, :700-719).
+ * pg_snapshot_cells_u8: a chunk of generator outputs -> cells first_cell .. first_cell + n - 1 of two uint8 HWC grid images on the device, each
+ *   (gh + 1) H x (gw + 1) W x 3; cell i sits at grid row 1 + i / gw, grid column 1 + i % gw (row 0 and column 0 hold the persons; not written here).
+ *   finetune_img float32 [n, 3, H, W] -> clip(rint((x + 1) * 127.5), 0, 255) in float32 without a fused multiply-add, rint half to even; NaN gives 0
+ *   (NumPy leaves that cast undefined).  pred_parsing float32 [n, C, H, W], 1 <= C <= 16 -> grey[k] on all three channels, k the FIRST index of the
+ *   maximal logit (a NaN logit never wins; all logits NaN or -inf: class 0); grey: C bytes in device memory.  W % 4 == 0, the float tensors 16-byte and the grids 4-byte aligned
+ *   (PG_ERR_UNSUPPORTED otherwise); first_cell < 0 or first_cell + n > gh * gw: PG_ERR_INVALID_ARG. */
+int pg_snapshot_cells_u8(const float* finetune_img, const float* pred_parsing, const unsigned char* grey, unsigned char* grid_img,
+                         unsigned char* grid_parsing, int n, int C, int H, int W, int gh, int gw, int first_cell, void* stream);
+int pg_snapshot_grid_abi_version(void);
 
 /* augment_plugin.so -- ADA discriminator augmentation (training/augment.py, AugmentPipe).  float32, dense NCHW, C <= 65535 / 4 per sample batch.
  * pg_augment_warp: x [n, c, h, w] -> y [n, c, 2(h+6), 2(w+6)]: reflect-pad by `margins` (device int32 [mx0, my0, mx1, my1], each clamped to

@@ -265,16 +265,11 @@ def _gpu_u8(img, device):
     return t.to(device).contiguous()
 
 
-def _warp_perspective_cpu(src, m, wh):
-    """The arithmetic of `warp_perspective_u8_kernel` (csrc/patch_routing.hip) in vectorised NumPy, for CPU tensors (config 1
-    runs the loader without a GPU): fp64 coordinates evaluated block origin + offset with separately rounded products and sums,
-    5 fractional bits, 15-bit bilinear weights, zero border."""
+def _warp_taps_cpu(m, wh, sh, sw):
+    """The taps of `warp_perspective_u8_kernel` (csrc/patch_routing.hip) for every destination pixel that reads at least one source pixel, in
+    vectorised NumPy: fp64 coordinates evaluated block origin + offset with separately rounded products and sums, 5 fractional bits, 15-bit
+    bilinear weights.  -> (flat destination indices, sy, sx, (w00, w01, w10, w11)); every other destination pixel is 0 (zero border)."""
     w, h = wh
-    a = src.numpy()
-    squeeze = a.ndim == 2
-    if squeeze:
-        a = a[:, :, None]
-    sh, sw, c = a.shape
     mi = invert3x3(m).reshape(9)
     bw = _block_width(h, w)
     ys, xs = np.mgrid[0:h, 0:w]
@@ -291,16 +286,38 @@ def _warp_perspective_cpu(src, m, wh):
     fY = np.clip((Y0 + mi[3] * x1) * W, -2147483648.0, 2147483647.0)
     X, Y = np.rint(fX).astype(np.int64), np.rint(fY).astype(np.int64)            # round half to even, as cvRound
     sx, sy = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
-    fx, fy = X & 31, Y & 31
+    idx = np.flatnonzero((sx >= -1) & (sx < sw) & (sy >= -1) & (sy < sh))          # (a pixel none of whose four taps is in range is 0)
+    sx, sy, fx, fy = sx.reshape(-1)[idx], sy.reshape(-1)[idx], (X & 31).reshape(-1)[idx], (Y & 31).reshape(-1)[idx]
     w00, w01, w10, w11 = (32 - fx) * (32 - fy) * 32, fx * (32 - fy) * 32, (32 - fx) * fy * 32, fx * fy * 32
     exact = (fx | fy) == 0
     w00, w11 = np.where(exact, 32767, w00), np.where(exact, 1, w11)
+    return idx, sy, sx, (w00, w01, w10, w11)
+
+
+def _warp_perspective_cpu(src, m, wh, cache=None):
+    """The arithmetic of `warp_perspective_u8_kernel` in NumPy, for CPU tensors (config 1 runs the loader without a GPU; `_warp_taps_cpu`).  `cache`, a
+    dict, keeps the taps per (matrix, sizes): warps of several sources through one matrix evaluate the coordinates once."""
+    w, h = wh
+    a = src.numpy()
+    squeeze = a.ndim == 2
+    if squeeze:
+        a = a[:, :, None]
+    sh, sw, c = a.shape
+    key = (np.asarray(m, np.float64).tobytes(), int(w), int(h), sh, sw)
+    taps = cache.get(key) if cache is not None else None
+    if taps is None:
+        taps = _warp_taps_cpu(m, wh, sh, sw)
+        if cache is not None:
+            cache[key] = taps
+    idx, sy, sx, (w00, w01, w10, w11) = taps
 
     def tap(yy, xx):
         ok = (yy >= 0) & (yy < sh) & (xx >= 0) & (xx < sw)
         return np.where(ok[..., None], a[np.clip(yy, 0, sh - 1), np.clip(xx, 0, sw - 1)], 0).astype(np.int64)
     v = (tap(sy, sx) * w00[..., None] + tap(sy, sx + 1) * w01[..., None] + tap(sy + 1, sx) * w10[..., None] + tap(sy + 1, sx + 1) * w11[..., None] + (1 << 14)) >> 15
-    out = np.clip(v, 0, 255).astype(np.uint8)
+    out = np.zeros((h * w, c), dtype=np.uint8)
+    out[idx] = np.clip(v, 0, 255).astype(np.uint8)
+    out = out.reshape(h, w, c)
     return torch.from_numpy(out[:, :, 0] if squeeze else out)
 
 

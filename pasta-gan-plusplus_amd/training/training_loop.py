@@ -1,12 +1,13 @@
 """The training driver: a dataset directory in, trained networks out (reference train.py + training/training_loop_fullbody.py, the parts this
 package supports).  `TrainFeed` (training/train_fetch.py) turns `TrainSet` items into rounds, `TrainingStep` runs the eight phases on them; this
 module builds the networks, runs the two until `kimg`, prints the reference's status line per tick (:669-679), appends the means of the loss reports to
-``stats.jsonl`` and writes snapshots.
+``stats.jsonl`` and writes snapshots: the networks, and -- for a dataset with at least three visualisation persons -- the reference's image grids
+(``init_denorm_{upper,lower}.png`` at start, ``fakesNNNNNN_{finetune,parsing}.png`` per image-snapshot tick; training/snapshot_grid.py).
 
 Snapshots are plain ``torch.save`` dicts of ``state_dict``s under the reference's parameter names -- ``G``, ``D``, ``D_parsing``, ``G_ema``,
 ``augment_p``, ``cur_nimg`` -- which ``--resume`` reads back; ``--resume`` also reads a reference snapshot (.pkl) through ``checkpoint.load_into``
 (nothing in it is executed).  Writing the reference's own pickle format is out of scope (its pickles embed module source), as are the VGG /
-contextual terms, metrics, image grids, zip datasets and tensorboard."""
+contextual terms, metrics, zip datasets and tensorboard."""
 
 import argparse
 import json
@@ -19,6 +20,7 @@ from . import augment
 from . import checkpoint
 from . import dataset as ds_mod
 from . import networks
+from . import snapshot_grid
 from . import train_fetch
 from .loss import StyleGAN2Loss
 from .training_step import TrainingStep
@@ -69,10 +71,16 @@ def format_time(seconds):
     return f'{s // 3600}h {s // 60 % 60:02d}m {s % 60:02d}s'
 
 
+def image_interval(snap, image_snap):
+    """Ticks between image snapshots: `snap` drives both kinds of snapshot, as in the reference, unless `image_snap` is given; 0 / None: none."""
+    return (snap if image_snap is None else image_snap) or 0
+
+
 def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, mask_weight=1.0, vgg_weight=0, contextual_weight=0, aug='ada', target=0.6,
-                  seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None):
+                  seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None):
     """Train on the dataset directory `data` for `kimg` thousand images (one process, one GPU: `batch` = `batch_gpu` x accumulation rounds).
-    Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied."""
+    Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied.
+    `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none)."""
     if batch % batch_gpu:
         raise ValueError('--batch must be a multiple of --batch-gpu')
     if aug not in ('ada', 'noaug'):
@@ -105,6 +113,17 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
     dataset = ds_mod.TrainSet(data, seed=seed, **(dataset_kwargs or {}))
     feed = train_fetch.TrainFeed(dataset, batch_gpu, rounds=batch // batch_gpu, seed=seed, workers=workers, device=dev, z_dim=G.z_dim)
 
+    image_snap = image_interval(snap, image_snap)
+    grid = None
+    if image_snap:
+        if len(dataset.vis_index) < 3:
+            print(f'Only {len(dataset.vis_index)} visualisation persons (train_img_front_vis_512_220414/): image snapshots are off.')
+        else:
+            print('Exporting sample images...')
+            grid = snapshot_grid.setup_snapshot_grid(dataset, dev)
+            for name, array in zip(('init_denorm_upper.png', 'init_denorm_lower.png'), grid.canvas_grids()):
+                snapshot_grid.save_png(os.path.join(run_dir, name), array)
+
     print(f'Training for {kimg} kimg...\n')
     start_time = tick_start_time = time.time()
     cur_tick, tick_start_nimg, maintenance_time = 0, step.cur_nimg, 0.0
@@ -125,6 +144,9 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
         with open(os.path.join(run_dir, 'stats.jsonl'), 'a') as f:
             f.write(json.dumps(dict(means, **{'Progress/tick': cur_tick, 'Progress/kimg': step.cur_nimg / 1e3, 'Progress/augment': p_now,
                                               'timestamp': time.time()})) + '\n')
+        if grid is not None and (done or cur_tick % image_snap == 0):
+            for name, array in zip(('finetune', 'parsing'), grid.render(G_ema, batch_gpu)):
+                snapshot_grid.save_png(os.path.join(run_dir, f'fakes{step.cur_nimg // 1000:06d}_{name}.png'), array)
         if snap is not None and (done or cur_tick % snap == 0):
             save_snapshot(os.path.join(run_dir, f'network-snapshot-{step.cur_nimg // 1000:06d}.pt'), G, D, D_parsing, G_ema, p_now, step.cur_nimg)
         cur_tick += 1
@@ -154,6 +176,7 @@ def parse_args(argv=None):
     p.add_argument('--kimg', type=float, default=25000, help='training length in thousands of images')
     p.add_argument('--tick', type=float, default=4, help='status line every so many thousand images')
     p.add_argument('--snap', type=int, default=50, help='snapshot every so many ticks')
+    p.add_argument('--image-snap', type=int, default=None, help='image grids every so many ticks (default: --snap; 0: none)')
     p.add_argument('--resume', help='a snapshot of this driver (.pt) or a reference network pickle (.pkl)')
     p.add_argument('--device', default='cuda')
     return p.parse_args(argv)
@@ -163,4 +186,4 @@ def main(argv=None):
     a = parse_args(argv)
     return training_loop(a.outdir, a.data, batch=a.batch, batch_gpu=a.batch_gpu, gamma=a.gamma, l1_weight=a.l1_weight, mask_weight=a.mask_weight,
                          vgg_weight=a.vgg_weight, contextual_weight=a.contextual_weight, aug=a.aug, target=a.target, seed=a.seed, workers=a.workers,
-                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device)
+                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap)
