@@ -14,6 +14,7 @@
  *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color
  *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8
  *   train_fetch_plugin.so   pg_train_fetch
+ *   tryon_front_plugin.so   pg_tryon_front_stats, pg_tryon_front_bit_rows, pg_tryon_front_compose
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 13
+#define PG_ABI_VERSION 14
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -714,6 +715,54 @@ typedef struct pg_train_io {
 } pg_train_io;
 int pg_train_fetch(const pg_train_io* io, int n, int H, int W, int h, int w, void* stream);
 int pg_train_fetch_abi_version(void);
+
+/* tryon_front_plugin.so -- the try-on loader's pre-routing maps on the GPU (training/tryon_front.py): everything ``TryOnTestSet.unrouted`` builds per
+ * pixel, from the decoded files and the key-point tables of ``TryOnTestSet.raw``, bit for bit (float64 in the loader's operation order, nothing
+ * contracted).  The frame is H x H; the W-wide sources sit at columns left : left + W of it (images pad with 255, everything else with 0).
+ * Three launches per batch, in this order on one stream, none of which reads anything back:
+ * pg_tryon_front_stats: zeroes stats (a memset node) and fills, per sample, PG_FRONT_STATS int32: the pixel counts of the label groups {5,7} {6} {9}
+ *   {12} of person_parsing [0..3] and clothes_parsing [4..7], H - (first row) of each group (0 = absent) [8..15], and the 3 x 256 histogram of the
+ *   person's image bytes under labels {10,13} [16..783] (bin 0 is not read: the skin medians ignore zero bytes).
+ * pg_tryon_front_bit_rows: bit_rows [n, 5, H, (H + 31) / 32] uint32, bit x % 32 of word x / 32 = pixel x: planes 0..3 the four arm bands (the
+ *   quadrilateral bands[i, b] dilated along x by 35 (upper arm) or 28 (fore-arm); b = 2 * arm + (0 upper arm, 1 fore-arm), arm 0 = label 14), plane 4 the mode's
+ *   canvas mask eroded along x (taps -4..+3, taps outside the frame ignored).  Reads stats (the canvas mask depends on the garment classes).
+ * pg_tryon_front_compose: resolves the per-sample decisions from stats (garment classes, dress rules, label, bound, the skin medians) and writes every
+ *   map of a ``collate_unrouted`` batch; finishes the dilation / erosion along y.  sleeve is written iff garment_parsing != NULL; canvas is not
+ *   written in PG_TRYON_FULL.
+ * H % 4 == 0, H <= 4096, 0 <= left, left + W <= H; pointers 4-byte aligned (PG_ERR_UNSUPPORTED otherwise). */
+#define PG_FRONT_STATS 784
+#define PG_FRONT_PRIMS 37                  /* rows of the pose table: 19 limbs + 18 joints */
+typedef struct pg_front_io {
+    const unsigned char* person_img;       /* [n, H, W, 3] as decoded */
+    const unsigned char* clothes_img;      /* [n, H, W, 3] */
+    const unsigned char* person_parsing;   /* [n, H, W] */
+    const unsigned char* clothes_parsing;  /* [n, H, W] */
+    const unsigned char* garment_parsing;  /* [n, H, W] or NULL (no sleeve mask) */
+    const int* pose_prims;                 /* [n, PG_FRONT_PRIMS, 8]: kind (0 none, 1 segment of thickness 5, 2 disc of radius 5), x0, y0, x1, y1, r, g, b;
+                                              integer coordinates in the W-wide frame, painting order */
+    const double* bands;                   /* [n, 4, 4, 2]: the arm bands' corners (x, y) in the H x H frame */
+    const int* band_absent;                /* [n, 4]: non-zero = no band: the whole hand label is removed */
+    const int* hip_top;                    /* [n, 2]: (valid, row) of the upper mode's hip rule; the row may be negative */
+    int* stats;                            /* [n, PG_FRONT_STATS] scratch */
+    unsigned int* bit_rows;                /* [n, 5, H, (H + 31) / 32] scratch */
+    unsigned char* upper_img;              /* [n, H, H, 3] */
+    unsigned char* lower_img;              /* [n, H, H, 3] */
+    unsigned char* upper_mask;             /* [n, H, H, 3] */
+    unsigned char* lower_mask;             /* [n, H, H, 3] */
+    unsigned char* sleeve;                 /* [n, H, H, 1] or NULL */
+    unsigned char* image;                  /* [n, H, H, 3] */
+    unsigned char* clothes;                /* [n, H, H, 3] */
+    unsigned char* pose;                   /* [n, H, H, 3] */
+    unsigned char* retain_mask;            /* [n, H, H, 1] */
+    unsigned char* canvas;                 /* [n, H, H, 3] or NULL (PG_TRYON_FULL) */
+    unsigned char* bound;                  /* [n, H] */
+    float* skin;                           /* [n, 3] */
+    int* label;                            /* [n] */
+} pg_front_io;
+int pg_tryon_front_stats(const pg_front_io* io, int n, int H, int W, void* stream);
+int pg_tryon_front_bit_rows(const pg_front_io* io, int n, int H, int W, int left, int mode, void* stream);
+int pg_tryon_front_compose(const pg_front_io* io, int n, int H, int W, int left, int mode, void* stream);
+int pg_tryon_front_abi_version(void);
 
 #ifdef __cplusplus
 }

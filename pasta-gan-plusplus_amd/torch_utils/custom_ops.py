@@ -43,6 +43,7 @@ PLUGIN_SOURCES = {
     'patch_routing_plugin': ['patch_routing.hip'],
     'augment_plugin': ['augment.hip'],
     'tryon_plugin': ['tryon.hip'],
+    'tryon_front_plugin': ['tryon_front.hip'],
     'train_fetch_plugin': ['train_fetch.hip'],
     'snapshot_grid_plugin': ['snapshot_grid.hip'],
     'conv2d_plugin': ['conv2d.hip', 'conv2d_inst_k3s1.hip', 'conv2d_inst_k1s1.hip', 'conv2d_inst_k2x2.hip', 'conv2d_inst_k2x1.hip',
@@ -51,7 +52,7 @@ PLUGIN_SOURCES = {
                       'conv2d16_inst_k1x2.hip', 'conv2d16_inst_k3s2.hip', 'conv2d16_inst_up2f.hip', 'conv1x1_head16.hip', 'optim.hip'],
 }
 
-ABI_VERSION = 13     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
+ABI_VERSION = 14     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
 
 _cached_plugins = dict()
 

@@ -43,6 +43,9 @@ KPT_COLORS = [[255, 0, 0], [255, 85, 0], [255, 170, 0], [255, 255, 0], [170, 255
 LIMBS = [[2, 3], [2, 6], [3, 4], [4, 5], [6, 7], [7, 8], [2, 9], [9, 10], [10, 11], [2, 12], [12, 13], [13, 14], [2, 1], [1, 15], [15, 17],
          [1, 16], [16, 18], [3, 17], [6, 18]]
 SIDE = 512
+PRIMS = len(LIMBS) + 18                               # rows of a pose table (PG_FRONT_PRIMS)
+ARMS = ((14, [5, 6, 7]), (15, [2, 3, 4]))             # (hand label, [shoulder, elbow, wrist]) of the palm masks
+BAND_K = (35, 28)                                     # dilation of the upper-arm and the fore-arm band (csrc/tryon_front.hip: kBandK)
 
 
 class _Raster:
@@ -194,24 +197,45 @@ class TryOnTestSet(torch.utils.data.Dataset):
 
     # ------------------------------------------------------------------ drawings
     @staticmethod
-    def pose_map(kp, size):
-        """Coloured skeleton (dataset.py:779-813): limbs as 5-pixel segments, joints as radius-5 discs; leg joints too close to
-        the frame are demoted to confidence 0.01 (the side effect the reference's drawing has on the keypoints)."""
+    def pose_table(kp, size):
+        """The primitives of the coloured skeleton (dataset.py:779-813) in painting order, as int32 [PRIMS, 8] rows of (kind, x0, y0, x1, y1, r, g, b):
+        kind 1 = a limb, a 5-pixel segment (x0, y0)-(x1, y1); kind 2 = a joint, a radius-5 disc at (x0, y0); kind 0 = unused row.  Leg joints too
+        close to the frame are demoted to confidence 0.01 (the side effect the reference's drawing has on the keypoints).  Returns (table, kp)."""
         h, w = size
-        canvas = np.zeros((h, w, 3), dtype=np.uint8)
+        table = np.zeros((PRIMS, 8), dtype=np.int32)
+        n = 0
         for i, (a, b) in enumerate(LIMBS):
             pa, pb = kp[a - 1], kp[b - 1]
             if pa[2] < 0.05 or pb[2] < 0.05:
                 continue
-            _Raster.segment(canvas, (int(pa[0]), int(pa[1])), (int(pb[0]), int(pb[1])), KPT_COLORS[i], 5)
+            table[n] = [1, int(pa[0]), int(pa[1]), int(pb[0]), int(pb[1])] + KPT_COLORS[i]
+            n += 1
         for i in range(len(kp)):
             if kp[i][2] < 0.05:
                 continue
             if i in (9, 10, 12, 13) and (kp[i][0] <= 0 or kp[i][1] <= 0 or kp[i][0] >= w - 50 or kp[i][1] >= h - 50):
                 kp[i][2] = 0.01
                 continue
-            _Raster.disc(canvas, (int(kp[i][0]), int(kp[i][1])), 5, KPT_COLORS[i])
-        return canvas, kp
+            table[n] = [2, int(kp[i][0]), int(kp[i][1]), 0, 0] + KPT_COLORS[i]
+            n += 1
+        return table, kp
+
+    @staticmethod
+    def draw_pose(table, size):
+        """The pose map uint8 [h, w, 3] of a `pose_table`: later rows paint over earlier ones."""
+        canvas = np.zeros((size[0], size[1], 3), dtype=np.uint8)
+        for kind, x0, y0, x1, y1, r, g, b in table.tolist():
+            if kind == 1:
+                _Raster.segment(canvas, (x0, y0), (x1, y1), [r, g, b], 5)
+            elif kind == 2:
+                _Raster.disc(canvas, (x0, y0), 5, [r, g, b])
+        return canvas
+
+    @staticmethod
+    def pose_map(kp, size):
+        """Coloured skeleton (dataset.py:779-813): limbs as 5-pixel segments, joints as radius-5 discs (`pose_table`, drawn)."""
+        table, kp = TryOnTestSet.pose_table(kp, size)
+        return TryOnTestSet.draw_pose(table, size), kp
 
     @staticmethod
     def _limb_band(a, b, c, d):
@@ -219,35 +243,43 @@ class TryOnTestSet(torch.utils.data.Dataset):
         ox, oy = (b - d) / 4.0, (c - a) / 4.0
         return [(a + ox, b + oy), (a - ox, b - oy), (c - ox, d - oy), (c + ox, d + oy)]
 
-    def _arm_masks(self, joints):
+    @staticmethod
+    def _arm_bands(joints):
+        """(upper-arm band, fore-arm band) of one arm's (shoulder, elbow, wrist): `_limb_band` corners, or None where a joint is missing."""
         (sx, sy, sc), (ex, ey, ec), (wx, wy, wc) = joints
-        upper = np.ones((SIDE, SIDE), dtype=bool)
-        lower = np.ones((SIDE, SIDE), dtype=bool)
-        if sc > 0.1 and ec > 0.1:
-            upper = _Raster.dilate(_Raster.quad(SIDE, SIDE, self._limb_band(sx, sy, ex, ey)), 35)
-        if ec > 0.1 and wc > 0.1:
-            lower = _Raster.dilate(_Raster.quad(SIDE, SIDE, self._limb_band(ex, ey, wx, wy)), 28)
+        upper = TryOnTestSet._limb_band(sx, sy, ex, ey) if sc > 0.1 and ec > 0.1 else None
+        lower = TryOnTestSet._limb_band(ex, ey, wx, wy) if ec > 0.1 and wc > 0.1 else None
         return upper, lower
+
+    def _arm_masks(self, joints):
+        """The two bands rasterised and dilated; a missing band is all ones (it removes the whole hand label)."""
+        bands = TryOnTestSet._arm_bands(joints)
+        return tuple(np.ones((SIDE, SIDE), dtype=bool) if band is None else _Raster.dilate(_Raster.quad(SIDE, SIDE, band), k)
+                     for band, k in zip(bands, BAND_K))
 
     def palm_mask(self, kp, parsing):
         """Hand label minus the upper-arm and fore-arm bands = the palms (dataset.py:753-777)."""
         out = np.zeros((SIDE, SIDE), dtype=bool)
-        for label, idx in ((14, [5, 6, 7]), (15, [2, 3, 4])):
+        for label, idx in ARMS:
             upper, lower = self._arm_masks(kp[idx])
             out |= (parsing[..., 0] == label) & ~upper & ~lower
         return out[..., None].astype(np.uint8)
 
     # ------------------------------------------------------------------ one pair
     def _person(self, person_name):
-        """The person side every mode shares (dataset.py:2031-2080 = :1330-1375 = :2807-2852): padded image, pose map and keypoints,
-        parsing, retain mask, the three skin medians (NaN where the neck and face hold no pixel)."""
+        """The person side every mode shares (dataset.py:2031-2080 = :1330-1375 = :2807-2852), from the files."""
         raw = self._image(person_name)
         assert raw.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
+        table, kp = self.pose_table(self._keypoints(person_name), raw.shape[:2])       # drawn in the unpadded frame, like the reference
+        kp[:, 0] += (SIDE - raw.shape[1]) // 2
+        return self._person_maps(raw, table, kp, self._labels('parsing', person_name))
+
+    def _person_maps(self, raw, table, kp, labels):
+        """padded image, pose map and keypoints, parsing, retain mask, the three skin medians (NaN where the neck and face hold no pixel) of a
+        decoded image [512, W, 3], its pose table, its keypoints (already in the padded frame) and its parsing [512, W, 1]."""
         image, left = _pad_square(raw, 255)
-        pose, kp = self.pose_map(self._keypoints(person_name), raw.shape[:2])          # drawn in the unpadded frame, like the reference
-        pose, _ = _pad_square(pose, 0)
-        kp[:, 0] += left
-        parsing, _ = _pad_square(self._labels('parsing', person_name), 0)
+        pose, _ = _pad_square(self.draw_pose(table, raw.shape[:2]), 0)
+        parsing, _ = _pad_square(labels, 0)
 
         is_ = lambda *labels: np.isin(parsing, labels).astype(np.uint8)
         retain_mask = is_(18, 19) + self.palm_mask(kp, parsing) + is_(1, 2, 4, 13)             # shoes + palms + head
@@ -275,10 +307,20 @@ class TryOnTestSet(torch.utils.data.Dataset):
         return clothes, clothes_pose, ckp, cparsing
 
     def _sleeve(self, name):
-        if not self.use_sleeve_mask:
-            return None
-        gp, _ = _pad_square(self._labels('garment_parsing', name), 0)
+        return self._sleeve_map(self._labels('garment_parsing', name)) if self.use_sleeve_mask else None
+
+    @staticmethod
+    def _sleeve_map(labels):
+        gp, _ = _pad_square(labels, 0)
         return np.isin(gp, (10, 11)).astype(np.uint8)
+
+    @staticmethod
+    def _hip_top(kp):
+        """Start of the lower garment by the hips (the upper mode's rule, `_host_upper`): an int, possibly negative, or None without both hips."""
+        lhip, rhip = kp[11], kp[8]
+        if lhip[2] > 0.05 and rhip[2] > 0.05:
+            return int((lhip[1] + rhip[1]) / 2 - 3 * np.linalg.norm(lhip[0:2] - rhip[0:2]) / 4)
+        return None
 
     def __getitem__(self, idx):
         clothes_name, person_name = self.pairs[idx]
@@ -299,13 +341,49 @@ class TryOnTestSet(torch.utils.data.Dataset):
         canvas                                         uint8 [512, 512, 3] or None: the mode's host-computed garment canvas -- the person's eroded
                                                        lower garment (upper) or eroded top (lower); None in the full mode
         person_name, clothes_name"""
-        clothes_name, person_name = self.pairs[idx]
+        return self._unrouted(*self.pairs[idx])
+
+    def _unrouted(self, clothes_name, person_name):
         h = getattr(self, '_host_' + self.part)(clothes_name, person_name)
         up, lo, um, lm, sleeve, ckp, kp = h['routing']
         return dict(upper_img=up, lower_img=lo, upper_mask=um, lower_mask=lm, sleeve=sleeve, clothes_kp=ckp, person_kp=kp, image=h['image'],
                     clothes=h['clothes'], pose=h['pose'], retain_mask=h['retain_mask'], skin=np.array(h['medians'], dtype=np.float64),
                     label=int(h['label']), bound=np.ascontiguousarray(h['bound'][:, 0, 0]), canvas=h['canvas'], person_name=person_name,
                     clothes_name=clothes_name)
+
+    def raw(self, idx):
+        """File decoding and keypoint arithmetic only -- what ``training.tryon_front.front_batch`` turns into the ``unrouted`` maps on the GPU.
+        A dict of
+
+        person_img, clothes_img            uint8 [512, W, 3] as decoded (not padded); person_parsing, clothes_parsing uint8 [512, W]
+        garment_parsing                    uint8 [512, W] or None: of the image the sleeve mask is read from (the clothes' in the upper and full modes,
+                                           the person's in the lower mode); None without use_sleeve_mask
+        person_kp, clothes_kp              float64 [18, 3], as ``unrouted`` returns them (leg joints demoted, x shifted into the padded frame)
+        pose_prims                         int32 [PRIMS, 8]: the person's `pose_table`
+        bands, band_absent                 float64 [4, 4, 2], int32 [4]: the `_limb_band` corners of the four arm bands (`ARMS` order, upper arm then
+                                           fore-arm) in the padded frame; absent = 1 where a joint is missing (the band is then "all ones")
+        hip_top                            `_hip_top` of the person: an int or None (read by the upper mode only)
+        person_name, clothes_name"""
+        clothes_name, person_name = self.pairs[idx]
+        person_img, clothes_img = self._image(person_name), self._image(clothes_name)
+        assert person_img.shape[0] == SIDE and clothes_img.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
+        table, kp = self.pose_table(self._keypoints(person_name), person_img.shape[:2])
+        kp[:, 0] += (SIDE - person_img.shape[1]) // 2
+        _, ckp = self.pose_table(self._keypoints(clothes_name), clothes_img.shape[:2])
+        ckp[:, 0] += (SIDE - clothes_img.shape[1]) // 2
+        bands, absent = np.zeros((4, 4, 2)), np.zeros(4, dtype=np.int32)
+        for arm, (_, idx3) in enumerate(ARMS):
+            for j, band in enumerate(self._arm_bands(kp[idx3])):
+                if band is None:
+                    absent[2 * arm + j] = 1
+                else:
+                    bands[2 * arm + j] = band
+        garment = None
+        if self.use_sleeve_mask:
+            garment = self._labels('garment_parsing', person_name if self.part == 'lower' else clothes_name)[..., 0]
+        return dict(person_img=person_img, clothes_img=clothes_img, person_parsing=self._labels('parsing', person_name)[..., 0],
+                    clothes_parsing=self._labels('parsing', clothes_name)[..., 0], garment_parsing=garment, person_kp=kp, clothes_kp=ckp,
+                    pose_prims=table, bands=bands, band_absent=absent, hip_top=self._hip_top(kp), person_name=person_name, clothes_name=clothes_name)
 
     # ------------------------------------------------------------------ the three modes: host half (before the routing), then the rest
     def _host_upper(self, clothes_name, person_name):
@@ -316,9 +394,8 @@ class TryOnTestSet(torch.utils.data.Dataset):
         lower_image = lower_mask * image
         lower_bbox = _bbox(lower_mask.copy())
         bound = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)
-        lhip, rhip = kp[11], kp[8]
-        if lhip[2] > 0.05 and rhip[2] > 0.05:                # start of the lower garment: the hips, or the parsing if that is higher
-            via_kps = int((lhip[1] + rhip[1]) / 2 - 3 * np.linalg.norm(lhip[0:2] - rhip[0:2]) / 4)
+        via_kps = self._hip_top(kp)
+        if via_kps is not None:                              # start of the lower garment: the hips, or the parsing if that is higher
             top = via_kps if lower_bbox is None else min(lower_bbox[1], via_kps)
             bound[top:] += 255                               # (NumPy slice semantics, negative values included, as in the reference)
         elif lower_bbox is not None:
@@ -463,6 +540,50 @@ def collate_unrouted(items, pin=False):
     for k in ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'):
         out[k] = [it[k] for it in items]
     return out
+
+
+_RAW_ARRAYS = ('person_img', 'clothes_img', 'person_parsing', 'clothes_parsing', 'garment_parsing', 'pose_prims', 'bands', 'band_absent')
+_HIP_CLAMP = 1 << 20                                  # far beyond the frame on either side: the slice ``bound[top:]`` is the same
+
+
+def collate_raw(items, pin=False):
+    """Stack ``TryOnTestSet.raw`` items into a batch: the arrays as [N, ...] tensors (pinned with pin=True, as `collate_unrouted`), garment_parsing None
+    without the sleeve mask, hip_top as int32 [N, 2] = (valid, row); keypoints and names stay lists."""
+    out = {}
+    for k in _RAW_ARRAYS:
+        out[k] = None if items[0][k] is None else torch.from_numpy(np.stack([it[k] for it in items]))
+    out['hip_top'] = torch.tensor([[0, 0] if it['hip_top'] is None else [1, max(-_HIP_CLAMP, min(_HIP_CLAMP, it['hip_top']))] for it in items],
+                                  dtype=torch.int32)
+    if pin:
+        out = {k: (None if v is None else v.pin_memory()) for k, v in out.items()}
+    for k in ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'):
+        out[k] = [it[k] for it in items]
+    return out
+
+
+class _RawPair(TryOnTestSet):
+    """One ``raw`` item behind the loader's host code: the readers of `_host_<part>` answer from the decoded arrays instead of the files."""
+
+    def __init__(self, item, part):
+        self.item, self.part, self.use_sleeve_mask, self.device = item, part, item['garment_parsing'] is not None, 'cpu'
+
+    def _person(self, person_name):
+        it = self.item
+        return self._person_maps(it['person_img'], it['pose_prims'], it['person_kp'].copy(), it['person_parsing'][..., None])
+
+    def _clothes(self, clothes_name):
+        it = self.item
+        clothes, _ = _pad_square(it['clothes_img'], 255)
+        cparsing, _ = _pad_square(it['clothes_parsing'][..., None], 0)
+        return clothes, None, it['clothes_kp'].copy(), cparsing         # (no clothes pose map: `unrouted` does not carry it)
+
+    def _sleeve(self, name):
+        return self._sleeve_map(self.item['garment_parsing'][..., None]) if self.use_sleeve_mask else None
+
+
+def unrouted_from_raw(item, part):
+    """``TryOnTestSet.unrouted`` of a ``raw`` item, through the same host statements (the CPU route of ``training.tryon_front.front_batch``)."""
+    return _RawPair(item, part)._unrouted(item['clothes_name'], item['person_name'])
 
 
 # ------------------------------------------------------------------------------------------------------------- the training set

@@ -2,7 +2,9 @@
 
 Per batch, on a GPU:
 
-1. ``TryOnTestSet.unrouted`` items (a DataLoader with `workers` processes, ``collate_unrouted``, pinned) are uploaded asynchronously;
+1. ``TryOnTestSet.unrouted`` items (a DataLoader with `workers` processes, ``collate_unrouted``, pinned) are uploaded asynchronously -- or, with
+   ``front='native'``, ``TryOnTestSet.raw`` items (``collate_raw``), from which ``tryon_front.front_batch`` builds the same batch on the device (three
+   native launches);
 2. ``patch_routing.normalize_batch(..., part=dataset.part)`` routes the whole batch (three native launches);
 3. ``pg_tryon_row_extent_u8`` finds the first / last row of the canvases the bound rules read, ``pg_tryon_inputs`` writes the seven float32
    generator inputs of ``dataset.to_generator_inputs`` (two launches, no host work between them);
@@ -263,6 +265,14 @@ class _Unrouted(torch.utils.data.Dataset):
         return self.dataset.unrouted(idx)
 
 
+class _Raw(_Unrouted):
+    def __getitem__(self, idx):
+        return self.dataset.raw(idx)
+
+
+FRONTS = ('host', 'native')
+
+
 def result_name(person_name, clothes_name):
     """test.py:183-186: the base names without their 4-character extensions."""
     return person_name.split('/')[-1][:-4] + '___' + clothes_name.split('/')[-1][:-4] + '.png'
@@ -273,15 +283,23 @@ def _write_png(path, rgb):
     PIL.Image.fromarray(rgb, 'RGB').save(path, compress_level=1)
 
 
-def run_tryon(dataset, G, outdir, batch_size=1, device='cuda', workers=0, stats=None):
+def run_tryon(dataset, G, outdir, batch_size=1, device='cuda', workers=0, stats=None, front='host'):
     """Try every pair of `dataset` (a ``TryOnTestSet``; its ``part`` picks the mode) on generator `G`, writing one PNG per pair into `outdir`.
-    Returns the list of files written, in pair order.  `stats`, a dict, receives per-batch host seconds waiting for the loader ('load_s'), and on a
-    GPU per-batch CUDA events ('events': (start, routed, inputs, generated, packed) per batch) -- read them after the call."""
+    Returns the list of files written, in pair order.  `front` picks who builds the pre-routing maps: 'host' -- the loader's workers
+    (``TryOnTestSet.unrouted``); 'native' -- the workers only decode (``TryOnTestSet.raw``) and ``tryon_front.front_batch`` builds the maps on the
+    device, between the upload and the routing (same images, byte for byte).  `stats`, a dict, receives per-batch host seconds waiting for the
+    loader ('load_s'), and on a GPU per-batch CUDA events ('events': (start, routed, inputs, generated, packed) per batch; with the native front
+    (start, front, routed, inputs, generated, packed)) -- read them after the call."""
+    if front not in FRONTS:
+        raise ValueError(f'front must be one of {FRONTS}, not {front!r}')
+    native = front == 'native'
+    if native:
+        from . import tryon_front
     dev = torch.device(device)
     cuda = dev.type == 'cuda'
     os.makedirs(outdir, exist_ok=True)
-    loader = torch.utils.data.DataLoader(_Unrouted(dataset), batch_size=batch_size, shuffle=False, num_workers=workers,
-                                         collate_fn=ds_mod.collate_unrouted, pin_memory=cuda)
+    loader = torch.utils.data.DataLoader((_Raw if native else _Unrouted)(dataset), batch_size=batch_size, shuffle=False, num_workers=workers,
+                                         collate_fn=ds_mod.collate_raw if native else ds_mod.collate_unrouted, pin_memory=cuda)
     written = []
     pending = []
 
@@ -309,23 +327,27 @@ def run_tryon(dataset, G, outdir, batch_size=1, device='cuda', workers=0, stats=
             names = list(zip(host_batch['person_name'], host_batch['clothes_name']))
             if cuda:
                 with torch.cuda.device(dev):
-                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if stats is not None else None
-                    if ev:
-                        ev[0].record()
+                    ev = []
+
+                    def mark():
+                        if stats is not None:
+                            ev.append(torch.cuda.Event(enable_timing=True))
+                            ev[-1].record()
+                    mark()
                     batch = upload(host_batch, dev)
+                    if native:
+                        batch = tryon_front.front_batch(batch, dataset.part)
+                        mark()
                     routed, ext = route(batch, dataset.part)
-                    if ev:
-                        ev[1].record()
+                    mark()
                     inp = batch_inputs(batch, routed, ext, dataset.part)
-                    if ev:
-                        ev[2].record()
+                    mark()
                     with torch.no_grad():
                         _, finetune_img, _ = G(**inp, noise_mode='const')
-                    if ev:
-                        ev[3].record()
+                    mark()
                     trip = triptych(finetune_img, batch['clothes'], batch['image'])
-                    if ev:
-                        ev[4].record()
+                    mark()
+                    if stats is not None:
                         stats.setdefault('events', []).append(ev)
                     host = torch.empty(trip.shape, dtype=torch.uint8, pin_memory=True)
                     host.copy_(trip, non_blocking=True)
@@ -333,7 +355,7 @@ def run_tryon(dataset, G, outdir, batch_size=1, device='cuda', workers=0, stats=
                     done.record()
                 item = (done, host, names)
             else:
-                item = (None, tryon_batch(host_batch, G, dataset.part), names)
+                item = (None, tryon_batch(tryon_front.front_batch(host_batch, dataset.part) if native else host_batch, G, dataset.part), names)
             if inflight is not None:                      # the previous batch's copy has had this batch's whole enqueue to land
                 flush(pool, inflight)
             inflight = item
@@ -357,6 +379,8 @@ def parse_args(argv=None):
     p.add_argument('--outdir', required=True, help='where the PNGs go')
     p.add_argument('--device', default='cuda', help="'cuda', 'cuda:<i>' or 'cpu' (plain torch and NumPy)")
     p.add_argument('--workers', type=int, default=0, help='DataLoader worker processes (the reference uses 0)')
+    p.add_argument('--front', choices=FRONTS, default='host', help="who builds the pre-routing maps: the loader's workers ('host') or the device "
+                   "('native': the workers only decode the files)")
     # accepted for the reference's command lines; the reference ignores them for try-on, and so does this driver
     p.add_argument('--seeds', help='ignored (as in the reference)')
     p.add_argument('--trunc', type=float, default=1.0, help='ignored (as in the reference)')
@@ -374,6 +398,6 @@ def main(argv=None):
     print(f'Loading networks from "{args.network}"...')
     G = build_generator(args.network, args.device)
     dataset = ds_mod.TryOnTestSet(args.dataroot, test_txt=args.testtxt, use_sleeve_mask=args.use_sleeve_mask, part=args.testpart)
-    files = run_tryon(dataset, G, args.outdir, batch_size=args.batchsize, device=args.device, workers=args.workers)
+    files = run_tryon(dataset, G, args.outdir, batch_size=args.batchsize, device=args.device, workers=args.workers, front=args.front)
     print(f'wrote {len(files)} images to {args.outdir}')
     return files
