@@ -7,7 +7,7 @@
  *   bias_act_plugin.so      pg_bias_act
  *   upfirdn2d_plugin.so     pg_upfirdn2d, pg_upfirdn2d_bias_act, pg_upfirdn2d_with_odd_samples
  *   conv2d_plugin.so        fp32: pg_conv2d_{packed_size,pack_weight,forward,splitk_plan,forward_splitk}, pg_conv2d_winograd_*,
- *                           pg_conv2d_up2_{forward,splitk_plan,forward_splitk}, pg_conv1x1_small, pg_conv3x3_cin1, pg_conv2d_wgrad{_plan,}, pg_split3_bf16_cl;
+ *                           pg_conv2d_up2_{forward,splitk_plan,forward_splitk}, pg_conv1x1_small, pg_conv1x1_fold_{prep,heads}, pg_conv3x3_cin1, pg_conv2d_wgrad{_plan,}, pg_split3_bf16_cl;
  *                           16-bit: pg_conv2d16_{packed_size,pack_weight,pack_weight_grouped,forward,splitk_plan,forward_splitk,up2_fused,wgrad,wgrad_plan,wgrad_x3}, pg_adam_flat_{chunk,step},
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 14
+#define PG_ABI_VERSION 15
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -355,6 +355,21 @@ int pg_conv2d_stem7x3_forward(const float* x, const void* packed, float* y, int 
  * styles / bias / skip may be NULL; clamp < 0 disables it.  PG_ERR_UNSUPPORTED otherwise (use pg_conv2d_forward). */
 int pg_conv1x1_small(const float* x, const float* w, const float* styles, const float* bias, const float* skip, float* y,
                      int N, int Cin, int64_t HW, int Cout, float scale, float clamp, void* stream);
+
+/* Folded heads: a linear 1x1 convolution over [x ; x2] followed by modulated linear 1x1 heads is one linear map of the two inputs per sample
+ * (csrc/conv1x1_fold.hip); where only the heads' results are consumed the intermediate feature map is never written.
+ *   pg_conv1x1_fold_prep:   w_out[n,o,c] = sum_k wh[o,k] * styles[n,k] * wm[k,c]          (wm [Cm, C] = the first convolution's weight with its gain applied)
+ *                           b_out[n,o]   = sum_k wh[o,k] * styles[n,k] * bm[k] + bh[o]     (bm [Cm], bh [Cout], styles [N, Cm] may be NULL)
+ *                           float64 accumulation in a fixed order; w_out [N, Cout, C], b_out [N, Cout].
+ *   pg_conv1x1_fold_heads:  r[n,o,p] = clamp(sum_{c < C1} x[n,c,p] * w[n,o,c] + sum_{c < C2} x2[n,c,p] * w[n,o,C1 + c] + bias[n,o]) (+ skip[n,o,p] for o < n_skip)
+ *                           channels [0, c_a) -> y_a [N, c_a, HW], channels [c_a, Cout) -> y_b [N, Cout - c_a, HW] (y_b NULL iff c_a == Cout);
+ *                           skip [N, n_skip, HW] (NULL iff n_skip == 0); clamp < 0 disables it.  One pass over x and x2 with 16-byte loads.
+ * float32 dense NCHW, Cout <= 16, HW % 4 == 0, 16-byte aligned tensors, (C1 + C2) * roundup(Cout, 4) * 4 bytes <= 64 KB; PG_ERR_UNSUPPORTED otherwise (run the
+ * two convolutions one after the other). */
+int pg_conv1x1_fold_prep(const float* wm, const float* bm, const float* wh, const float* bh, const float* styles, float* w_out, float* b_out,
+                         int N, int Cm, int C, int Cout, void* stream);
+int pg_conv1x1_fold_heads(const float* x, const float* x2, const float* w, const float* bias, const float* skip, float* y_a, float* y_b,
+                          int N, int C1, int C2, int64_t HW, int Cout, int c_a, int n_skip, float clamp, void* stream);
 
 /* 3x3 convolution of a one-channel image (first layer of the SPADE blocks on the parsing / mask map, networks.py:1708-1712):
  * y = act(conv2d(x [N,1,H,W], w [Cout,1,3,3] * scale, padding=1)), cross-correlation as F.conv2d; act = PG_ACT_LINEAR | PG_ACT_RELU

@@ -172,6 +172,10 @@ def _init(plugin_name='conv2d_plugin'):
         lib.pg_conv3x3_cin1.argtypes = [vp, vp, vp, i, i, i, i, f, i, vp]
         lib.pg_conv1x1_small.restype = i
         lib.pg_conv1x1_small.argtypes = [vp] * 6 + [i, i, i64, i, f, f, vp]
+        lib.pg_conv1x1_fold_prep.restype = i
+        lib.pg_conv1x1_fold_prep.argtypes = [vp] * 7 + [i, i, i, i, vp]
+        lib.pg_conv1x1_fold_heads.restype = i
+        lib.pg_conv1x1_fold_heads.argtypes = [vp] * 7 + [i, i, i, i64, i, i, i, f, vp]
         _plugin = plugin
     return _plugin
 
@@ -741,6 +745,50 @@ def conv1x1_small(x, weight, styles=None, bias=None, skip=None, scale=1.0, clamp
                                   float(scale), float(clamp) if clamp is not None else -1.0, nat.stream_of(x))
     nat.check(rc, 'pg_conv1x1_small')
     return y
+
+
+def conv1x1_fold_ok(x, x2, skip=None):
+    """Shapes the folded-heads kernel takes (csrc/conv1x1_fold.hip): two float32 dense NCHW inputs of one batch and image size, H*W a multiple of 4."""
+    return (x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x2.dtype == torch.float32 and x2.is_cuda and x2.is_contiguous()
+            and x.shape[0] == x2.shape[0] and x.shape[2:] == x2.shape[2:] and (x.shape[2] * x.shape[3]) % 4 == 0
+            and (skip is None or (skip.dtype == torch.float32 and skip.is_cuda and skip.is_contiguous() and skip.shape[0] == x.shape[0] and skip.shape[2:] == x.shape[2:])))
+
+
+def conv1x1_fold_prep(wm, bm, wh, bh, styles):
+    """Per-sample composition of `heads o merge`: wm [Cm, C] (the merge weight with its gain applied), bm [Cm] | None, wh [Cout, Cm], bh [Cout] | None,
+    styles [N, Cm] -> w [N, Cout, C] = (wh * styles[n]) @ wm and b [N, Cout] = (wh * styles[n]) @ bm + bh, accumulated in float64 (one launch)."""
+    lib = _init().lib
+    wm, bm, wh, bh, styles = _f32c(wm, 'wm'), _f32c(bm, 'bm'), _f32c(wh, 'wh'), _f32c(bh, 'bh'), _f32c(styles, 'styles')
+    cm, c = wm.shape
+    cout, n = int(wh.shape[0]), int(styles.shape[0])
+    if tuple(wh.shape) != (cout, cm) or tuple(styles.shape) != (n, cm) or (bm is not None and bm.numel() != cm) or (bh is not None and bh.numel() != cout):
+        raise nat.NativeOpError('conv1x1_fold_prep: wm [Cm, C], bm [Cm], wh [Cout, Cm], bh [Cout], styles [N, Cm]')
+    w = torch.empty([n, cout, c], dtype=torch.float32, device=wm.device)
+    b = torch.empty([n, cout], dtype=torch.float32, device=wm.device)
+    with torch.cuda.device(wm.device):
+        rc = lib.pg_conv1x1_fold_prep(nat.ptr(wm), nat.ptr(bm), nat.ptr(wh), nat.ptr(bh), nat.ptr(styles), nat.ptr(w), nat.ptr(b), n, cm, c, cout, nat.stream_of(wm))
+    nat.check(rc, 'pg_conv1x1_fold_prep')
+    return w, b
+
+
+def conv1x1_fold_heads(x, x2, w, b, c_a, skip=None, clamp=None):
+    """clamp(w[n] @ [x ; x2] + b[n]) (+ skip on the first skip.shape[1] channels) in one streaming pass over x and x2: w [N, Cout, C1 + C2], b [N, Cout]
+    (`conv1x1_fold_prep`).  Returns (y_a [N, c_a, H, W], y_b [N, Cout - c_a, H, W] | None).  Raises NativeNotCovered for shapes the kernel declines."""
+    lib = _init().lib
+    x, x2, w, b, skip = _f32c(x, 'x'), _f32c(x2, 'x2'), _f32c(w, 'w'), _f32c(b, 'b'), _f32c(skip, 'skip')
+    n, c1, h, wd = x.shape
+    c2, cout, c_a = int(x2.shape[1]), int(w.shape[1]), int(c_a)
+    n_skip = int(skip.shape[1]) if skip is not None else 0
+    if (tuple(x2.shape) != (n, c2, h, wd) or tuple(w.shape) != (n, cout, c1 + c2) or tuple(b.shape) != (n, cout) or not 0 < c_a <= cout
+            or (skip is not None and (tuple(skip.shape) != (n, n_skip, h, wd) or n_skip > cout))):
+        raise nat.NativeOpError('conv1x1_fold_heads: x [N, C1, H, W], x2 [N, C2, H, W], w [N, Cout, C1 + C2], b [N, Cout], skip [N, <= Cout, H, W]')
+    ya = torch.empty([n, c_a, h, wd], dtype=torch.float32, device=x.device)
+    yb = torch.empty([n, cout - c_a, h, wd], dtype=torch.float32, device=x.device) if c_a < cout else None
+    with torch.cuda.device(x.device):
+        rc = lib.pg_conv1x1_fold_heads(nat.ptr(x), nat.ptr(x2), nat.ptr(w), nat.ptr(b), nat.ptr(skip), nat.ptr(ya), nat.ptr(yb), n, c1, c2, h * wd, cout, c_a,
+                                       n_skip, float(clamp) if clamp is not None else -1.0, nat.stream_of(x))
+    nat.check(rc, 'pg_conv1x1_fold_heads')
+    return ya, yb
 
 
 def modconv_dcoefs(weight, styles, scale=1.0):

@@ -1222,14 +1222,59 @@ class _SynthesisBlockBase(nn.Module):
             self.merge_conv = Conv2dLayer(out_channels + 64, out_channels, kernel_size=1, resample_filter=resample_filter, channels_last=self.channels_last)
         if self.TEXTURE:
             self.spade_b512 = Spade_ResBlockV4_512(out_channels, out_channels, spade_channels=1)
+        self._fold_cache = _PackCache()
 
     def affine_layers(self):
         """(layer, index of its w within the block's ws, gain folded into its styles) in call order."""
         convs = [self.conv1] if self.in_channels == 0 else [self.conv0, self.conv1]
         return [(m, i, 1.0) for i, m in enumerate(convs)] + ([(self.torgb, self.num_conv, self.torgb.weight_gain)] if self.has_torgb else [])
 
-    def _forward(self, x, img, ws, pose_feature, cat_feat, parsing, force_fp32, fused_modconv, styles=None, **layer_kwargs):
-        """`styles` (private): the block's affine outputs in `affine_layers()` order when the network computed them for all layers at once."""
+    def _heads_folded(self, x, feat, w, styles, img):
+        """fp32 inference, style blocks: merge_conv (linear, bias, no clamp) and the ToRGB heads behind it are one linear map of (x, feat) per sample,
+        head([x ; feat]) = (W_head o s_n) (g W_m [x ; feat] + b_m) + b_head; one streaming pass over the two inputs computes the heads without the merged
+        feature map (csrc/conv1x1_fold.hip).  Returns (rgb, pred_parsing), or None where the route or the kernel does not cover the call (the caller then
+        runs the two layers one after the other).  PG_HEAD_FOLD=0: never (A/B runs)."""
+        mc, tr = getattr(self, 'merge_conv', None), getattr(self, 'torgb', None)
+        if mc is None or tr is None or self.TEXTURE or self.architecture != 'skip' or os.environ.get('PG_HEAD_FOLD', '1') == '0' or os.environ.get('PG_HEAD_STREAM', '1') == '0':
+            return None
+        if (mc.conv_clamp is not None or mc.activation != 'linear' or mc.up != 1 or mc.down != 1 or tuple(mc.weight.shape[2:]) != (1, 1)
+                or tuple(tr.weight.shape[2:]) != (1, 1) or int(mc.weight.shape[1]) != int(x.shape[1]) + int(feat.shape[1])):
+            return None
+        parsing = tr.is_last and tr.is_style
+        params = [mc.weight, tr.weight, tr.bias] + ([mc.bias] if mc.bias is not None else []) + ([tr.m_weight1, tr.m_bias1] if parsing else [])
+        if not (_fast_ok(x, feat, styles, img, tr.affine.weight, tr.affine.bias, *params) and conv2d_mfma.conv1x1_fold_ok(x, feat, img)):
+            return None
+
+        def build():
+            cm = int(mc.weight.shape[0])
+            heads = [(tr.weight, tr.bias)] + ([(tr.m_weight1, tr.m_bias1)] if parsing else [])
+            return ((mc.weight.detach().float().reshape(cm, -1) * mc.weight_gain * mc.act_gain).contiguous(),
+                    (mc.bias.detach().float() * mc.act_gain).contiguous() if mc.bias is not None else None,
+                    torch.cat([hw.detach().float().reshape(hw.shape[0], cm) for hw, _ in heads]).contiguous(),
+                    torch.cat([hb.detach().float() for _, hb in heads]).contiguous())
+        wm, bm, wh, bh = self._fold_cache.get(('fold',), params, build)
+        if styles is None:
+            styles = tr.affine(w) * tr.weight_gain
+        try:
+            wn, bn = conv2d_mfma.conv1x1_fold_prep(wm, bm, wh, bh, styles)
+            return conv2d_mfma.conv1x1_fold_heads(x, feat, wn, bn, int(tr.weight.shape[0]), skip=img, clamp=tr.conv_clamp)
+        except nat.NativeNotCovered:
+            return None
+
+    def _merge_heads(self, x, feat, w, styles, img, fused_modconv, feat_unused=False):
+        """merge_conv over [x ; feat], then img + ToRGB (and the parsing head): (x, rgb, pred_parsing).  `feat_unused`: nothing reads the merged feature map
+        but the heads -- it is then not computed where `_heads_folded` covers the call, and x comes back as None."""
+        if feat_unused:
+            heads = self._heads_folded(x, feat, w, styles, img)
+            if heads is not None:
+                return (None,) + tuple(heads)
+        x = self.merge_conv(x, x2=feat)
+        rgb, pred_parsing = self.torgb(x, w, fused_modconv=fused_modconv, skip_img=img, styles=styles)
+        return x, rgb, pred_parsing
+
+    def _forward(self, x, img, ws, pose_feature, cat_feat, parsing, force_fp32, fused_modconv, styles=None, _feat_unused=False, **layer_kwargs):
+        """`styles` (private): the block's affine outputs in `affine_layers()` order when the network computed them for all layers at once.
+        `_feat_unused` (private): the caller does not read the returned feature map (the network's last style block); it may come back as None."""
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
         half = self.use_fp16 and not force_fp32
         fmt = dict(dtype=torch.float16 if half else torch.float32,
@@ -1252,7 +1297,15 @@ class _SynthesisBlockBase(nn.Module):
             else:
                 x = conv(self.conv1, conv(self.conv0, x, 0), 1)
                 if self.resolution > 32:   # mix in the warped-garment feature map: conv1x1(cat([x, feat])) without the copy
-                    x = self.merge_conv(x, x2=cat_feat[str(self.resolution)].to(**fmt))
+                    feat = cat_feat[str(self.resolution)].to(**fmt)
+                    if _feat_unused and self.has_torgb and not self.TEXTURE and not half:
+                        # the merged map feeds only the heads: they are computed from (x, feat) directly where the folded kernel covers the call
+                        if img is not None:
+                            misc.assert_shape(img, [None, self.img_channels, self.resolution // 2, self.resolution // 2])
+                            img = upfirdn2d.upsample2d(img, self.resample_filter)
+                        x, rgb, pred_parsing = self._merge_heads(x, feat, style(self.num_conv), st[self.num_conv], img, fused_modconv, feat_unused=True)
+                        return x, rgb.to(dtype=torch.float32, memory_format=torch.contiguous_format), pred_parsing
+                    x = self.merge_conv(x, x2=feat)
                 if self.TEXTURE:
                     x = self.spade_b512(x, parsing)
 
@@ -1270,8 +1323,8 @@ class SynthesisBlockFull_v1_v6(_SynthesisBlockBase):
     """Style-branch block (networks.py:2086-2194)."""
     TORGB = ToRGBLayerFull_v1_v5
 
-    def forward(self, x, img, ws, pose_feature, cat_feat, force_fp32=False, fused_modconv=None, styles=None, **layer_kwargs):
-        return self._forward(x, img, ws, pose_feature, cat_feat, None, force_fp32, fused_modconv, styles=styles, **layer_kwargs)
+    def forward(self, x, img, ws, pose_feature, cat_feat, force_fp32=False, fused_modconv=None, styles=None, _feat_unused=False, **layer_kwargs):
+        return self._forward(x, img, ws, pose_feature, cat_feat, None, force_fp32, fused_modconv, styles=styles, _feat_unused=_feat_unused, **layer_kwargs)
 
 
 class SynthesisBlockFull_v1_v4(_SynthesisBlockBase):
@@ -1412,7 +1465,9 @@ class SynthesisNetworkFull_v18(nn.Module):
         x = img = pred_parsing = None
         kept = {}
         for res, w in zip(self.block_resolutions, styles):
-            x, img, pred_parsing = getattr(self, f'b{res}')(x, img, w, pose_feat, cat_feat, force_fp32=True, styles=pre[res] if pre is not None else None, **block_kwargs)
+            # (the last style block's feature map is read by nobody -- the texture branch starts from kept[256] --: the block may fold its merge_conv into its heads)
+            x, img, pred_parsing = getattr(self, f'b{res}')(x, img, w, pose_feat, cat_feat, force_fp32=True, styles=pre[res] if pre is not None else None,
+                                                            _feat_unused=(res == self.block_resolutions[-1]), **block_kwargs)
             kept[res] = (x, img)       # neither is modified in place afterwards: no clone needed
         x_256, img_256 = kept[self.block_resolutions[-2]]
 
