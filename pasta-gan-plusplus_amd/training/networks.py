@@ -20,6 +20,7 @@ Both run only on the GPU; there is no CPU path.
 """
 
 import os
+from typing import NamedTuple, Optional
 import numpy as np
 import torch
 import torch.nn as nn
@@ -261,205 +262,218 @@ def _up2_fused_weights(wt_iohw, fy):
     return torch.cat(out, dim=1).contiguous()
 
 
+def _up2_transposed_weight(weight, flip_weight):
+    """The float32 IOHW weight conv2d_resample hands conv_transpose2d: O <-> I transposed, flipped iff flip_weight (its `not flip_weight` twist)."""
+    wt = weight.detach().float().transpose(0, 1)
+    return (wt.flip([2, 3]) if flip_weight else wt).contiguous()
+
+
 def _up2_fused_cached(cache, weight, flip_weight, resample_filter):
     """([Cin, 4 Cout, 3, 2] stack, 2 * fx as four floats) of an up = 2 layer, once per weight version."""
     def build():
         fy, fx = _separable_taps(resample_filter)
-        wt = weight.detach().float().transpose(0, 1)
-        return _up2_fused_weights((wt.flip([2, 3]) if flip_weight else wt).contiguous(), fy), [2.0 * float(v) for v in fx]
+        return _up2_fused_weights(_up2_transposed_weight(weight, flip_weight), fy), [2.0 * float(v) for v in fx]
     return cache.get(('up2_fusedx', flip_weight), [weight], build)
 
 
 def _up2_composite_cached(cache, weight, flip_weight, resample_filter):
     """The four composite 3x3 phase kernels of an up = 2 layer ({(a, b): [Cin, Cout, 3, 3]}), once per weight version."""
-    def build():
-        wt = weight.detach().float().transpose(0, 1)
-        return _up2_composite_phases((wt.flip([2, 3]) if flip_weight else wt).contiguous(), resample_filter.float())
-    return cache.get(('up2_composite', flip_weight), [weight], build)
+    return cache.get(('up2_composite', flip_weight), [weight],
+                     lambda: _up2_composite_phases(_up2_transposed_weight(weight, flip_weight), resample_filter.float()))
 
 
-def _up2_wcat_cached(cache, weight, flip_weight, resample_filter):
-    """The same four kernels stacked along Cout ([Cin, 4 Cout, 3, 3]) for the one-launch form."""
-    return cache.get(('up2_cat', flip_weight), [weight],
-                     lambda: torch.cat(list(_up2_composite_cached(cache, weight, flip_weight, resample_filter).values()), dim=1).contiguous())
+R16_UP1 = 'up1'                             # the forms of a 16-bit modulated convolution (`_Route16.form`).  up = 1: one launch
+R16_FUSED_X = 'up2_fused_x'                 # up = 2, one launch: the y half of the FIR in the weights, its x half in the epilogue (`_up2_fused_weights`)
+R16_COMPOSITE = 'up2_composite'             # up = 2, one four-phase launch of the composite 3x3 kernels (`_up2_composite_phases`) stacked along Cout
+R16_COMPOSITE_X4 = 'up2_composite_x4'       # up = 2, the same kernels as four launches (a Cout the four-phase launch does not cover, or PG_UP2_MERGED=0)
+R16_MERGED_T = 'up2_merged_t'               # up = 2, the transposed convolution's phases as ONE launch of 2x2 kernels (`_up2_transposed_phases_2x2`), then the FIR
+R16_TRANSPOSED = 'up2_transposed'           # up = 2, every other shape: the transposed convolution's phases, one launch each, then the FIR
+_R16_TAPS = {R16_FUSED_X: 24, R16_COMPOSITE: 36, R16_COMPOSITE_X4: 36, R16_MERGED_T: 16}        # packed tap slots per weight; the other forms pack kh * kw
 
 
-def _modconv16_policy(weight_shape, hw, up, padding, resample_filter):
-    """Which form a 16-bit modulated convolution takes (pure host logic, shared by `_modconv_fast16` and the stack's batched style preparation):
-    (composite, merged_t, shared, tpad, fir_pad, fused_x) -- `shared` = one weight pack for the batch with x * styles and demodulation as the epilogue scale;
-    `fused_x` (round 5) = the one-launch form with the y half of the FIR in the weights and its x half in the epilogue (`_up2_fused_weights`): 18 tap-products
-    per input position instead of the composite's 36 (the reference's transposed convolution has 9 + the FIR pass)."""
+class _Route16(NamedTuple):
+    """How one 16-bit modulated convolution runs: `form` = one of the R16_* above; `shared` = one weight pack for the batch, with x * styles and demodulation as
+    the epilogue's scale, instead of one pack per sample; `tpad` / `fir_pad` = the paddings of the transposed convolution and of the FIR (None for up = 1)."""
+    form: str
+    shared: bool
+    tpad: Optional[tuple]
+    fir_pad: Optional[list]
+
+
+def _modconv16_route(weight_shape, hw, up, padding, resample_filter):
+    """The route of a 16-bit modulated convolution: pure host logic over the shapes, read by `_modconv_fast16` and by the stack's batched preparation
+    (`SynthesisStack._prepare_all`); nothing else decides any part of it.  The environment is read on every call."""
     cout, cin, kh, kw = (int(v) for v in weight_shape)
     h, w = (int(v) for v in hw)
-    tpad = fir_pad = None
-    merged_t = False
-    composite = False
+    env = os.environ.get
+    form, tpad, fir_pad = R16_UP1, None, None
     if up == 2:
         fw, fh = upfirdn2d._get_filter_size(resample_filter)
         tpad, fir_pad = _up2_geometry(kh, kw, fw, fh, padding)
+        form = R16_TRANSPOSED
+        policy = env('PG_UP2_POLICY', 'composite')
+        weight_bound = cout * 36 > 2 * h * w
+        four_phase = conv2d_mfma16.phases_supported(cout)       # the four phases stacked along Cout, ONE launch
         composite = ((kh, kw, fw, fh) == (3, 3, 4, 4) and tuple(tpad) == (0, 0) and list(fir_pad) == [1, 1, 1, 1] and resample_filter.ndim == 2
-                     and os.environ.get('PG_UP2_COMPOSITE', '1') != '0')
+                     and env('PG_UP2_COMPOSITE', '1') != '0')
         # Per-layer policy, measured in round 4 (VERDICT r3 item 2) and NOT adopted: the composite kernel has 36 taps per output phase set where the
         # reference's transposed convolution has 9 (conv2d_resample.py:125-142) -- 4x the multiplies and 4x the packed weights -- so the layers with
         # Cout * 36 > 2 * H * W (the 8^2 ... 64^2 inputs of the 1024-wide stack) were tried as the transposed convolution's four phases on ONE shared
         # weight pack + the channels-last FIR (PG_UP2_POLICY=auto).  Those layers are latency-bound, not multiply-bound: four phase launches of
         # 30-97 us + the FIR pass against ONE composite launch of 69-137 us -- config 5 2023 -> 1696 images/s on the same box
         # (profiles/r04_cfg5_up2_policy.txt).  What would pay is the four transposed phases as ONE launch (taps zero-padded to 2x2: 16 instead of 36).
-        if composite and cout * 36 > 2 * h * w and os.environ.get('PG_UP2_POLICY', 'composite') == 'auto':
-            composite = False
-        # ... which is the `merged` policy (PG_UP2_POLICY=merged): the four transposed phases as 2x2 kernels (16 taps, 9 non-zero) stacked along Cout, ONE
-        # launch (two-role form, 16 x 16-pixel tiles) into a (2H+2) x (2W+2) buffer, then the channels-last FIR with the fused tail on its [2H+1, 2W+1]
-        # view, for the weight-dominated layers with H >= 32.  Built, parity-green (tests/test_conv16.py::test_up2_layer_routes_vs_oracle) and measured:
-        # 512 -> 256 at 64^2 116 + FIR vs 143 us composite, 1024 -> 512 at 32^2 157 + FIR vs 144 us (the (H+1) x (W+1) = 33 x 33 positions pad 16 x 16 tiles
-        # by 44 %, 64 K chunks per tile stay latency-bound); config 5 1882 vs 1921 images/s -- NOT adopted either.
-        merged_t = (composite and cout * 36 > 2 * h * w and min(h, w) >= int(os.environ.get('PG_UP2_MERGED_T_MIN', '32')) and conv2d_mfma16.phases_supported(cout)
-                    and os.environ.get('PG_UP2_POLICY', 'composite') == 'merged')
-        if merged_t:
-            composite = False
+        if composite and not (weight_bound and policy == 'auto'):
+            # ... which is the `merged` policy (PG_UP2_POLICY=merged): the four transposed phases as 2x2 kernels (16 taps, 9 non-zero) stacked along Cout, ONE
+            # launch (two-role form, 16 x 16-pixel tiles) into a (2H+2) x (2W+2) buffer, then the channels-last FIR with the fused tail on its [2H+1, 2W+1]
+            # view, for the weight-dominated layers with H >= 32.  Built, parity-green (tests/test_conv16.py::test_up2_layer_routes_vs_oracle) and measured:
+            # 512 -> 256 at 64^2 116 + FIR vs 143 us composite, 1024 -> 512 at 32^2 157 + FIR vs 144 us (the (H+1) x (W+1) = 33 x 33 positions pad 16 x 16 tiles
+            # by 44 %, 64 K chunks per tile stay latency-bound); config 5 1882 vs 1921 images/s -- NOT adopted either.
+            if weight_bound and min(h, w) >= int(env('PG_UP2_MERGED_T_MIN', '32')) and four_phase and policy == 'merged':
+                form = R16_MERGED_T
+            # fused-x (round 5): 18 tap-products per input position instead of the composite's 36 (the reference's transposed convolution has 9 + the FIR pass)
+            elif (cin % 16 == 0 and cin >= 32 and cout % 32 == 0 and min(h, w) >= int(env('PG_UP2_FUSEDX_MIN', '32')) and env('PG_UP2_FUSEDX', '1') != '0'
+                  and _separable_taps(resample_filter) is not None):
+                form = R16_FUSED_X
+            else:
+                form = R16_COMPOSITE if four_phase and env('PG_UP2_MERGED', '1') != '0' else R16_COMPOSITE_X4
     # Weight-dominated layers (the low-resolution blocks: N per-sample copies of a 512..1024-channel kernel outweigh the
     # activations): the reference's NON-fused form (networks.py:73-84; its own choice for half precision at batch > 1,
     # networks.py:2152-2154) -- x * styles, ONE shared weight pack cached across steps, demodulation as the epilogue's
     # per-(n, cout) scale.  Styles are normalised per sample like networks.py:57-59 so that x * s stays in 16-bit range;
     # the factor returns through dcoefs (computed from the normalised styles).
-    merged_t = up == 2 and merged_t
-    fused_x = (composite and cin % 16 == 0 and cin >= 32 and cout % 32 == 0 and min(h, w) >= int(os.environ.get('PG_UP2_FUSEDX_MIN', '32'))
-               and os.environ.get('PG_UP2_FUSEDX', '1') != '0' and _separable_taps(resample_filter) is not None)
-    if fused_x:
-        composite = False
-    taps = 36 if composite else (24 if fused_x else (16 if merged_t else kh * kw))
-    shared = cout * taps > float(os.environ.get('PG_MODCONV16_SHARED_RATIO', '1')) * h * w and os.environ.get('PG_MODCONV16_SHARED', '1') != '0'
+    shared = cout * _R16_TAPS.get(form, kh * kw) > float(env('PG_MODCONV16_SHARED_RATIO', '1')) * h * w and env('PG_MODCONV16_SHARED', '1') != '0'
+    return _Route16(form, shared, tpad, fir_pad)
 
-    return composite, merged_t, shared, tpad, fir_pad, fused_x
+
+class _PackSource16(NamedTuple):
+    """What the one weight pack of a single-pack route is built from: the float32 tensor with pack_weight's `flip` / `transpose_oi`, whether the demodulation
+    coefficients repeat four times along Cout (the stacked phases of an up = 2 layer), and the layer-cache tag of its shared pack."""
+    w: torch.Tensor
+    flip: bool
+    transpose_oi: bool
+    repeat4: bool
+    shared_tag: tuple
+
+
+def _modconv16_pack_source(cache, weight, flip_weight, resample_filter, route):
+    """The `_PackSource16` of a layer on `route`, or None for the forms that run on more than one pack (four composite launches, the transposed phases)."""
+    if route.form == R16_UP1:
+        return _PackSource16(weight.detach().float(), not flip_weight, False, False, ('shared', flip_weight))
+    if route.form == R16_FUSED_X:
+        return _PackSource16(_up2_fused_cached(cache, weight, flip_weight, resample_filter)[0], False, True, True, ('up2_fusedx_shared', flip_weight))
+    if route.form == R16_COMPOSITE:         # the four composite kernels stacked along Cout: [Cin, 4 Cout, 3, 3]
+        wcat = cache.get(('up2_cat', flip_weight), [weight],
+                         lambda: torch.cat(list(_up2_composite_cached(cache, weight, flip_weight, resample_filter).values()), dim=1).contiguous())
+        return _PackSource16(wcat, False, True, True, ('up2_cat_shared', flip_weight))
+    if route.form == R16_MERGED_T:
+        wcat = cache.get(('up2_t_cat', flip_weight), [weight], lambda: _up2_transposed_phases_2x2(_up2_transposed_weight(weight, flip_weight)))
+        return _PackSource16(wcat, False, True, True, ('up2_t_cat_shared', flip_weight))
+    return None
+
+
+def _modconv16_pack(cache, weight, src, shared, dtype, s32, dcoefs):
+    """(packed, per-sample stride) of `src`: the shared pack from the layer cache; else the pack the stack's batch left for this layer
+    (`SynthesisStack._prepare_all`); else T(w * styles * dcoefs) packed here (networks.py:85-94)."""
+    if shared:
+        return cache.get(src.shared_tag + (dtype,), [weight], lambda: conv2d_mfma16.pack_weight(src.w, dtype, flip=src.flip, transpose_oi=src.transpose_oi)[0]), 0
+    hit = conv2d_mfma16.pack_lookup(src.w, dtype, src.flip, src.transpose_oi, s32)
+    if hit is not None:
+        return hit
+    if dcoefs is not None and src.repeat4:
+        dcoefs = dcoefs.repeat(1, 4)
+    return conv2d_mfma16.pack_weight(src.w, dtype, flip=src.flip, transpose_oi=src.transpose_oi, styles=s32, dcoefs=dcoefs)[:2]
+
+
+def _noise_phase_major(cache, noise, h, w):
+    """Phase-major copy [B, 2, 2, h, w] of an output-resolution noise map, one pass; the constant map of inference (one tensor per parameter version,
+    SynthesisLayer.forward) is copied once per version."""
+    if noise is None:
+        return None
+    build = lambda: noise.reshape(-1, h, 2, w, 2).permute(0, 2, 4, 1, 3).contiguous()
+    return build() if noise.requires_grad or noise.ndim != 2 else cache.get(('noise_phases',), [noise], build)
 
 
 def _modconv_fast16(x, weight, styles, noise, up, padding, resample_filter, demodulate, flip_weight, cache, epilogue):
-    """bf16 / fp16 inference route: the reference's fused form (networks.py:85-94) -- per-sample weights
-    T(w * styles * dcoefs) -- packed by one small kernel, then ONE launch of the 16-bit MFMA convolution per output phase
-    with noise / bias / activation / gain / clamp (/ residual) in its epilogue.  up=2 with the usual 3x3 kernel and 4-tap
-    filter runs as four 3x3 launches on composite weights (`_up2_composite_phases`); other up=2 shapes as the transposed
-    convolution's phases followed by the FIR pass that also carries the tail."""
+    """bf16 / fp16 inference route: the reference's fused form (networks.py:85-94) -- per-sample weights T(w * styles * dcoefs) packed by one small
+    kernel -- or, where `route.shared`, its non-fused form on one pack for the batch; then the launches of `route.form` (`_modconv16_route`) with noise / bias /
+    activation / gain / clamp (/ residual) in the epilogue of the convolution or, for the two forms that end in the FIR, of that pass."""
     cout, cin, kh, kw = (int(v) for v in weight.shape)
     n, _, h, w = x.shape
     cache = cache if cache is not None else _PackCache()
     ep = dict(epilogue) if epilogue else {}
-    w32, s32 = weight.detach().float(), styles.detach().float()
-    composite, merged_t, shared, tpad, fir_pad, fused_x = _modconv16_policy((cout, cin, kh, kw), (h, w), up, padding, resample_filter)
-    out_scale = None
-    w2 = cache.get(('w2',), [weight], lambda: conv2d_mfma.modconv_w2(w32)) if demodulate else None
+    s32 = styles.detach().float()
+    route = _modconv16_route((cout, cin, kh, kw), (h, w), up, padding, resample_filter)
+    form, shared, tpad, fir_pad = route
+    out_scale = dcoefs = None
+    w2 = cache.get(('w2',), [weight], lambda: conv2d_mfma.modconv_w2(weight.detach().float())) if demodulate else None
     if shared:          # one launch: per-sample maximum, normalised styles (float32 + 16-bit), coefficients of the normalised styles
         out_scale, s32, s16 = conv2d_mfma.modconv_prep(w2, s32, cout, normalize=True, demodulate=demodulate, half_dtype=x.dtype)
         x = x * s16[:, :, None, None]
-        dcoefs = None
-    else:
-        dcoefs = conv2d_mfma.modconv_prep(w2, s32, cout)[0] if demodulate else None
-    if up == 1:
+    elif demodulate:
+        dcoefs = conv2d_mfma.modconv_prep(w2, s32, cout)[0]
+
+    def single_pack():
+        src = _modconv16_pack_source(cache, weight, flip_weight, resample_filter, route)
+        return _modconv16_pack(cache, weight, src, shared, x.dtype, s32, dcoefs)
+    if form == R16_UP1:
         if not conv2d_mfma16.supported(kh, kw, 1):
             return None
-        if shared:
-            packed = cache.get(('shared', flip_weight, x.dtype), [weight], lambda: conv2d_mfma16.pack_weight(w32, x.dtype, flip=not flip_weight)[0])
-            return conv2d_mfma16.conv2d_forward(x, packed, cout, kh, kw, pad=(padding, padding), sample_stride=0, out_scale=out_scale, noise=noise, **ep)
-        hit = conv2d_mfma16.pack_lookup(w32, x.dtype, not flip_weight, False, s32)           # packed with the rest of the stack's layers (SynthesisStack._prepare_all)?
-        packed, per = hit if hit is not None else conv2d_mfma16.pack_weight(w32, x.dtype, flip=not flip_weight, styles=s32, dcoefs=dcoefs)[:2]
-        return conv2d_mfma16.conv2d_forward(x, packed, cout, kh, kw, pad=(padding, padding), sample_stride=per, noise=noise, **ep)
-    out_hw = ((h - 1) * 2 - 2 * tpad[0] + kh, (w - 1) * 2 - 2 * tpad[1] + kw)
-
-    def transposed_weight():
-        wt = w32.transpose(0, 1)
-        return (wt.flip([2, 3]) if flip_weight else wt).contiguous()
-    if fused_x:
-        wcat, fir_x = _up2_fused_cached(cache, weight, flip_weight, resample_filter)
-        res = ep.pop('residual', None)
-        noise_phases = None
-        if noise is not None:           # phase-major copy of the noise map ([B, 2, 2, h, w]; the constant map of inference once per parameter version)
-            if noise.requires_grad or noise.ndim != 2:
-                noise_phases = noise.reshape(-1, h, 2, w, 2).permute(0, 2, 4, 1, 3).contiguous()
-            else:
-                noise_phases = cache.get(('noise_phases',), [noise], lambda: noise.reshape(-1, h, 2, w, 2).permute(0, 2, 4, 1, 3).contiguous())
-        if shared:
-            packed = cache.get(('up2_fusedx_shared', flip_weight, x.dtype), [weight], lambda: conv2d_mfma16.pack_weight(wcat, x.dtype, transpose_oi=True)[0])
-            per = 0
-        else:
-            hit = conv2d_mfma16.pack_lookup(wcat, x.dtype, False, True, s32)
-            if hit is not None:
-                packed, per = hit
-            else:
-                packed, per, _ = conv2d_mfma16.pack_weight(wcat, x.dtype, transpose_oi=True, styles=s32, dcoefs=dcoefs.repeat(1, 4) if dcoefs is not None else None)
+        packed, per = single_pack()
+        return conv2d_mfma16.conv2d_forward(x, packed, cout, kh, kw, pad=(padding, padding), sample_stride=per, out_scale=out_scale, noise=noise, **ep)
+    res = ep.pop('residual', None)
+    if form == R16_FUSED_X:
+        fir_x = _up2_fused_cached(cache, weight, flip_weight, resample_filter)[1]
+        noise_phases = _noise_phase_major(cache, noise, h, w)
+        packed, per = single_pack()
         y = conv2d_mfma16.conv_up2_fused(x, packed, cout, fir_x, sample_stride=per, out_scale=out_scale, noise=noise_phases, **ep)
-        return y if res is None else y.add_(res)
-    if composite:
-        phases = _up2_composite_cached(cache, weight, flip_weight, resample_filter)
+    elif form in (R16_COMPOSITE, R16_COMPOSITE_X4):
         y = torch.empty([n, cout, 2 * h, 2 * w], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         xcl = conv2d_mfma16.to_channels_last(x)
-        res = ep.pop('residual', None)
-        if noise is not None:           # phase-major copy of the noise map, one pass: [B, 2, 2, h, w]
-            if noise.requires_grad or noise.ndim != 2:
-                noise_phases = noise.reshape(-1, h, 2, w, 2).permute(0, 2, 4, 1, 3).contiguous()
-            else:       # the constant noise map of inference (one tensor per parameter version, SynthesisLayer.forward): its phase-major copy is made once
-                noise_phases = cache.get(('noise_phases',), [noise], lambda: noise.reshape(-1, h, 2, w, 2).permute(0, 2, 4, 1, 3).contiguous())
-        if conv2d_mfma16.phases_supported(cout) and os.environ.get('PG_UP2_MERGED', '1') != '0':
-            # all four phases in ONE launch: their kernels stacked along Cout (block 2a + b), each cout block written to its own
-            # output phase -- the input is read once, a quarter of the launches and of the split-K shares
-            wcat = _up2_wcat_cached(cache, weight, flip_weight, resample_filter)
-            if shared:
-                packed = cache.get(('up2_cat_shared', flip_weight, x.dtype), [weight], lambda: conv2d_mfma16.pack_weight(wcat, x.dtype, transpose_oi=True)[0])
-                per = 0
-            else:
-                hit = conv2d_mfma16.pack_lookup(wcat, x.dtype, False, True, s32)
-                if hit is not None:
-                    packed, per = hit
-                else:
-                    packed, per, _ = conv2d_mfma16.pack_weight(wcat, x.dtype, transpose_oi=True, styles=s32, dcoefs=dcoefs.repeat(1, 4) if dcoefs is not None else None)
-            conv2d_mfma16.conv2d_forward(xcl, packed, cout, 3, 3, pad=(1, 1), out_hw=(h, w), y=y, sample_stride=per, out_scale=out_scale,
-                                         noise=noise_phases if noise is not None else None, phases=True, **ep)
-            return y if res is None else y.add_(res)
-        if shared:
-            packs = cache.get(('up2_shared', flip_weight, x.dtype), [weight],
-                              lambda: {ab: conv2d_mfma16.pack_weight(wab, x.dtype, transpose_oi=True)[0] for ab, wab in phases.items()})
-        else:                           # the four per-sample phase packs in one launch
-            stacked = cache.get(('up2_stacked', flip_weight), [weight], lambda: torch.stack(list(phases.values())).contiguous())
-            packed_all, per = conv2d_mfma16.pack_weight_grouped(stacked, x.dtype, transpose_oi=True, styles=s32, dcoefs=dcoefs)
-        for g, ((a, b), wab) in enumerate(phases.items()):
-            packed = packs[(a, b)] if shared else packed_all[g]
-            per = 0 if shared else per
-            nz = None
-            if noise is not None:       # the phase's samples of the output-resolution noise map
-                nz = noise_phases[:, a, b]
-            conv2d_mfma16.conv2d_forward(xcl, packed, cout, 3, 3, pad=(1, 1), out_hw=(h, w), y=y, out_step=(2, 2), out_off=(a, b), sample_stride=per,
-                                         out_scale=out_scale, noise=nz, **ep)
-        return y if res is None else y.add_(res)
-    if merged_t:
-        wcat = cache.get(('up2_t_cat', flip_weight), [weight], lambda: _up2_transposed_phases_2x2(transposed_weight()))
-        if shared:      # x already carries the normalised styles; demodulation is a per-(n, cout) scale, which commutes with the FIR that follows
-            packed = cache.get(('up2_t_cat_shared', flip_weight, x.dtype), [weight], lambda: conv2d_mfma16.pack_weight(wcat, x.dtype, transpose_oi=True)[0])
-            per = 0
+        noise_phases = _noise_phase_major(cache, noise, h, w)
+        if form == R16_COMPOSITE:
+            # cout block 2a + b is written to output phase (a, b): the input is read once, a quarter of the launches and of the split-K shares
+            packed, per = single_pack()
+            conv2d_mfma16.conv2d_forward(xcl, packed, cout, 3, 3, pad=(1, 1), out_hw=(h, w), y=y, sample_stride=per, out_scale=out_scale, noise=noise_phases,
+                                         phases=True, **ep)
         else:
-            packed, per, _ = conv2d_mfma16.pack_weight(wcat, x.dtype, transpose_oi=True, styles=s32, dcoefs=dcoefs.repeat(1, 4) if dcoefs is not None else None)
-        ybuf = torch.empty([n, cout, 2 * h + 2, 2 * w + 2], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        conv2d_mfma16.conv2d_forward(conv2d_mfma16.to_channels_last(x), packed, cout, 2, 2, pad=(1, 1), out_hw=(h + 1, w + 1), y=ybuf, sample_stride=per,
-                                     out_scale=out_scale, phases=True)
-        y = ybuf[:, :, :2 * h + 1, :2 * w + 1]                    # a pitched channels-last view: the FIR below reads it in place
-    elif shared:        # x already carries the normalised styles; demodulation is a per-(n, cout) scale, which commutes with the FIR that follows
-        phases = cache.get(('up2_t_shared', flip_weight, x.dtype, tuple(tpad), (h, w)), [weight],
-                           lambda: conv2d_mfma16.pack_transposed(transposed_weight(), x.dtype, 2, tpad, (h, w), out_hw))
+            phases = _up2_composite_cached(cache, weight, flip_weight, resample_filter)
+            if shared:
+                packs, per = cache.get(('up2_shared', flip_weight, x.dtype), [weight],
+                                       lambda: [conv2d_mfma16.pack_weight(wab, x.dtype, transpose_oi=True)[0] for wab in phases.values()]), 0
+            else:                       # the four per-sample phase packs in one launch
+                stacked = cache.get(('up2_stacked', flip_weight), [weight], lambda: torch.stack(list(phases.values())).contiguous())
+                packs, per = conv2d_mfma16.pack_weight_grouped(stacked, x.dtype, transpose_oi=True, styles=s32, dcoefs=dcoefs)
+            for packed, (a, b) in zip(packs, phases):       # each phase with its samples of the output-resolution noise map
+                conv2d_mfma16.conv2d_forward(xcl, packed, cout, 3, 3, pad=(1, 1), out_hw=(h, w), y=y, out_step=(2, 2), out_off=(a, b), sample_stride=per,
+                                             out_scale=out_scale, noise=noise_phases[:, a, b] if noise is not None else None, **ep)
     else:
-        phases = conv2d_mfma16.pack_transposed(transposed_weight(), x.dtype, 2, tpad, (h, w), out_hw, styles=s32, dcoefs=dcoefs)
-    if not merged_t:
-        if phases is None:
-            return None
-        y = conv2d_mfma16.conv_transpose2d_forward(x, phases, cout, out_hw, stride=2, **(dict(out_scale=out_scale) if shared and out_scale is not None else {}))
-    res = ep.pop('residual', None)
-    b = ep.get('bias')
-    fused = upfirdn2d.upfirdn2d_bias_act(y, resample_filter, padding=fir_pad, gain=4, noise=noise, b=b, act=ep.get('act', 'linear'),
-                                         alpha=ep.get('alpha') or 0.0, act_gain=ep.get('gain', 1.0), clamp=ep.get('clamp'))
-    if fused is None:
-        if not y.is_contiguous(memory_format=torch.channels_last):
-            y = y.contiguous(memory_format=torch.channels_last)      # (the fused FIR declined the pitched view of the merged route: dense copy)
-        y = upfirdn2d.upfirdn2d(y, resample_filter, padding=fir_pad, gain=4)
-        if noise is not None:
-            y = y.add_(noise.to(y.dtype))
-        fused = bias_act.bias_act(y, b.to(y.dtype) if b is not None else None, act=ep.get('act', 'linear'), alpha=ep.get('alpha'),
-                                  gain=ep.get('gain', 1.0), clamp=ep.get('clamp'))
-    return fused if res is None else fused.add_(res)
+        # the FIR pass follows and carries the tail; where the pack is shared, demodulation is a per-(n, cout) scale, which commutes with the FIR
+        if form == R16_MERGED_T:
+            packed, per = single_pack()
+            ybuf = torch.empty([n, cout, 2 * h + 2, 2 * w + 2], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            conv2d_mfma16.conv2d_forward(conv2d_mfma16.to_channels_last(x), packed, cout, 2, 2, pad=(1, 1), out_hw=(h + 1, w + 1), y=ybuf, sample_stride=per,
+                                         out_scale=out_scale, phases=True)
+            y = ybuf[:, :, :2 * h + 1, :2 * w + 1]                    # a pitched channels-last view: the FIR below reads it in place
+        else:
+            out_hw = ((h - 1) * 2 - 2 * tpad[0] + kh, (w - 1) * 2 - 2 * tpad[1] + kw)
+            pack = lambda **kw_: conv2d_mfma16.pack_transposed(_up2_transposed_weight(weight, flip_weight), x.dtype, 2, tpad, (h, w), out_hw, **kw_)
+            phases = cache.get(('up2_t_shared', flip_weight, x.dtype, tuple(tpad), (h, w)), [weight], pack) if shared else pack(styles=s32, dcoefs=dcoefs)
+            if phases is None:
+                return None
+            y = conv2d_mfma16.conv_transpose2d_forward(x, phases, cout, out_hw, stride=2, **(dict(out_scale=out_scale) if out_scale is not None else {}))
+        b = ep.get('bias')
+        fused = upfirdn2d.upfirdn2d_bias_act(y, resample_filter, padding=fir_pad, gain=4, noise=noise, b=b, act=ep.get('act', 'linear'),
+                                             alpha=ep.get('alpha') or 0.0, act_gain=ep.get('gain', 1.0), clamp=ep.get('clamp'))
+        if fused is None:
+            if not y.is_contiguous(memory_format=torch.channels_last):
+                y = y.contiguous(memory_format=torch.channels_last)      # (the fused FIR declined the pitched view of the merged route: dense copy)
+            y = upfirdn2d.upfirdn2d(y, resample_filter, padding=fir_pad, gain=4)
+            if noise is not None:
+                y = y.add_(noise.to(y.dtype))
+            fused = bias_act.bias_act(y, b.to(y.dtype) if b is not None else None, act=ep.get('act', 'linear'), alpha=ep.get('alpha'),
+                                      gain=ep.get('gain', 1.0), clamp=ep.get('clamp'))
+        y = fused
+    return y if res is None else y.add_(res)
 
 
 fused_training_modconv = os.environ.get('PG_TRAIN_MODCONV', '1') != '0'    # False / PG_TRAIN_MODCONV=0: the differentiable composition (any order of derivative)
@@ -1584,49 +1598,33 @@ class SynthesisStack(nn.Module):
     def _prepare_all(self, styles, force_fp32):
         """Inference: the style preparation of every modulated 3x3 convolution of the stack (demodulation coefficients; for the layers that share one
         weight pack also the per-sample normalised styles in 16 bits, networks.py:57-59) as ONE launch instead of one ~8 us launch per layer
-        (`pg_modconv_prep_batched`); each layer's own `modconv_prep` call then finds its result waiting.  The per-layer form is decided by the same
-        `_modconv16_policy` the layers use."""
-        jobs, half_dtype = [], None
+        (`pg_modconv_prep_batched`); each layer's own `modconv_prep` call then finds its result waiting.  Each 16-bit layer is prepared for the
+        `_modconv16_route` it will take: the route says whether it shares a pack, and `_modconv16_pack_source` what its per-sample pack is built from."""
+        jobs, per_sample, half_dtype = [], [], None
         for res in self.block_resolutions:
             block = getattr(self, f'b{res}')
             half = block.half_dtype is not None and not force_fp32
             for k, (m, _, _) in enumerate(block.affine_layers()[:block.num_conv]):
-                cout = int(m.weight.shape[0])
-                shared = False
-                if half:
-                    shared = _modconv16_policy(m.weight.shape, (res // m.up, res // m.up), m.up, m.padding, m.resample_filter)[2]
-                    half_dtype = block.half_dtype
+                route = _modconv16_route(m.weight.shape, (res // m.up, res // m.up), m.up, m.padding, m.resample_filter) if half else None
+                half_dtype = block.half_dtype if half else half_dtype
                 w2 = m._cache.get(('w2',), [m.weight], lambda m=m: conv2d_mfma.modconv_w2(m.weight.detach().float()))
-                jobs.append((w2, styles[res][k], cout, shared, True))
+                jobs.append((w2, styles[res][k], int(m.weight.shape[0]), half and route.shared, True))
+                # (the batched pack kernel has the 3x3 and 3x2 layouts, not the 2x2 one of the merged-t form)
+                if half and not route.shared and route.form != R16_MERGED_T and tuple(m.weight.shape[2:]) == (3, 3) and m.weight.dtype == torch.float32:
+                    per_sample.append((m, styles[res][k], route))
         if not (jobs and len(jobs) <= conv2d_mfma.PREP_MAX_JOBS and len({j[1].shape[0] for j in jobs}) == 1):
             return
         conv2d_mfma.modconv_prep_batched(jobs, half_dtype=half_dtype)
         if half_dtype is None or os.environ.get('PG_PACK_BATCHED', '1') == '0':
             return
-        # ... and the per-sample weight packs of the layers that do not share one pack (T(w * styles * dcoefs), networks.py:85-94), also one launch: each
+        # ... and the per-sample weight packs of the layers that run on one pack of their own (T(w * styles * dcoefs), networks.py:85-94), also one launch: each
         # layer's `pack_lookup` finds its pack waiting.  The demodulation coefficients are the ones the launch above is producing (same stream: ordered).
         packs = []
-        for res in self.block_resolutions:
-            block = getattr(self, f'b{res}')
-            if block.half_dtype is None or force_fp32:
-                continue
-            for k, (m, _, _) in enumerate(block.affine_layers()[:block.num_conv]):
-                if tuple(m.weight.shape[2:]) != (3, 3) or m.weight.dtype != torch.float32:
-                    continue
-                cout = int(m.weight.shape[0])
-                composite, merged_t, shared, _, _, fused_x = _modconv16_policy(m.weight.shape, (res // m.up, res // m.up), m.up, m.padding, m.resample_filter)
-                if shared or merged_t:
-                    continue
-                s = styles[res][k]
-                dcoefs = conv2d_mfma.modconv_prep_peek(s)
-                if dcoefs is None:
-                    continue
-                if m.up == 1:
-                    packs.append((m.weight.detach(), False, False, s, dcoefs))            # flip_weight = True for up = 1 layers: correlation, no flip
-                elif fused_x:
-                    packs.append((_up2_fused_cached(m._cache, m.weight, False, m.resample_filter)[0], False, True, s, dcoefs))
-                elif composite and conv2d_mfma16.phases_supported(cout) and os.environ.get('PG_UP2_MERGED', '1') != '0':
-                    packs.append((_up2_wcat_cached(m._cache, m.weight, False, m.resample_filter), False, True, s, dcoefs))
+        for m, s, route in per_sample:
+            dcoefs = conv2d_mfma.modconv_prep_peek(s)
+            src = _modconv16_pack_source(m._cache, m.weight, m.up == 1, m.resample_filter, route) if dcoefs is not None else None       # (flip_weight as SynthesisLayer.forward passes it)
+            if src is not None:
+                packs.append((src.w, src.flip, src.transpose_oi, s, dcoefs))
         if 0 < len(packs) <= conv2d_mfma16.PACK_MAX_JOBS:
             conv2d_mfma16.pack_weight_batched(packs, half_dtype)
 

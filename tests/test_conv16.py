@@ -558,3 +558,83 @@ def test_graphed_forward_replays_the_stack():
     assert torch.equal(fwd(ws_b), eager_b)
     assert torch.equal(fwd(ws_a), eager_a)
     assert not torch.equal(eager_a, eager_b)
+
+
+# (layer, form, shared) of the 128^2 stack below, worked out on the CPU from the 16-bit route rules: the low resolutions share one weight pack, the high ones pack per sample
+_BATCH_PLAN = [('b8.conv1', 'up1', True), ('b16.conv0', 'composite x1', True), ('b16.conv1', 'up1', True), ('b32.conv0', 'composite x1', True), ('b32.conv1', 'up1', False),
+               ('b64.conv0', 'fused-x', True), ('b64.conv1', 'up1', False), ('b128.conv0', 'fused-x', False), ('b128.conv1', 'up1', False)]
+
+
+@pytest.mark.parametrize('fusedx', ['1', '0'], ids=['fusedx', 'composite'])
+def test_stack_batched_preparation_matches_the_layers(fusedx, monkeypatch):
+    """SynthesisStack._prepare_all packs the per-sample weights of the whole stack in one launch, by its own reading of each layer's route; a layer whose reading
+    differs packs again and nothing else notices.  On a 128^2 bf16 stack (widths 64, 64, 64, 64, 32; N = 2) that holds every batched kind -- shared-pack layers,
+    per-sample up = 1 layers, a per-sample fused-x layer (b128.conv0: 32 * 24 <= 64 * 64) and, with PG_UP2_FUSEDX=0, the same layer as a per-sample composite in
+    one launch (32 * 36 <= 64 * 64) --:  the plan the layers follow when they pack for themselves is the one worked out above; the batch holds exactly its
+    per-sample layers; no layer packs a 3x3 / 3x2 kernel per sample during the batched forward; both registries are empty when the forward clears them; and the
+    image equals the unbatched one bit for bit (same kernels, same operands)."""
+    from detgen import fill_module_
+    from training import networks as PN
+    from torch_utils.ops import conv2d_mfma, conv2d_mfma16 as M
+    monkeypatch.setenv('PG_UP2_FUSEDX', fusedx)
+    net = fill_module_(PN.SynthesisStack(w_dim=64, img_resolution=128, channel_base=4096, channel_max=64, num_fp16_res=5, half_dtype=torch.bfloat16,
+                                         conv_clamp=256), 'plan.').to(DEV).eval()
+    ws = torch.randn([2, net.num_ws, 64], generator=torch.Generator().manual_seed(9)).to(DEV)
+    current, packs, batches, left = [None], [], [], []
+    for name, m in net.named_modules():
+        if isinstance(m, PN.SynthesisLayer):
+            m.register_forward_pre_hook(lambda mod, args, name=name: current.__setitem__(0, name))
+    pack_weight, pack_weight_grouped, pack_weight_batched, pack_clear, prep_clear = M.pack_weight, M.pack_weight_grouped, M.pack_weight_batched, M.pack_clear, conv2d_mfma.modconv_prep_clear
+
+    def form(w, transpose_oi, grouped):
+        k = tuple(w.shape[-2:])
+        return 'composite x4' if grouped else {(3, 2): 'fused-x', (2, 2): 'merged-t', (3, 3): 'composite x1' if transpose_oi else 'up1'}.get(k, f'{k[0]}x{k[1]}')
+
+    def spy_pack(w, dtype, *args, **kw):
+        packs.append((current[0], form(w, kw.get('transpose_oi', False), False), kw.get('styles') is None))
+        return pack_weight(w, dtype, *args, **kw)
+
+    def spy_grouped(ws_, dtype, *args, **kw):
+        packs.append((current[0], form(ws_, True, True), kw.get('styles') is None))
+        return pack_weight_grouped(ws_, dtype, *args, **kw)
+
+    def spy_batched(jobs, dtype):
+        batches.append(len(jobs))
+        return pack_weight_batched(jobs, dtype)
+
+    def spy_clear(clear):
+        def run():
+            left.append((len(conv2d_mfma._prep_registry), len(M._pack_registry)))
+            return clear()
+        return run
+    monkeypatch.setattr(M, 'pack_weight', spy_pack)
+    monkeypatch.setattr(M, 'pack_weight_grouped', spy_grouped)
+    monkeypatch.setattr(M, 'pack_weight_batched', spy_batched)
+    monkeypatch.setattr(M, 'pack_clear', spy_clear(pack_clear))
+    monkeypatch.setattr(conv2d_mfma, 'modconv_prep_clear', spy_clear(prep_clear))
+    k3 = ('up1', 'fused-x', 'composite x1', 'composite x4')         # the forms with 3x3 / 3x2 kernels (the ToRGB heads are 1x1)
+
+    # every layer packs for itself (cold caches: the shared packs show too): the plan
+    monkeypatch.setenv('PG_PACK_BATCHED', '0')
+    monkeypatch.setenv('PG_PREP_BATCHED', '0')
+    with torch.no_grad():
+        want = net(ws, noise_mode='const').clone()
+    plan = [p for p in packs if p[1] in k3]
+    for name, kind, shared in plan:
+        print(f'{name}: {kind}, {"shared" if shared else "per-sample"}')
+    expected = [(n_, 'composite x1' if (fusedx == '0' and k == 'fused-x') else k, s) for n_, k, s in _BATCH_PLAN]
+    assert plan == expected and not batches
+    per_sample = [p for p in plan if not p[2] and p[1] != 'composite x4']
+    assert len(per_sample) >= 4
+
+    # the stack prepares them in one batch
+    del packs[:], left[:]
+    monkeypatch.setenv('PG_PACK_BATCHED', '1')
+    monkeypatch.setenv('PG_PREP_BATCHED', '1')
+    with torch.no_grad():
+        got = net(ws, noise_mode='const').clone()
+    print(f'batched: {batches} jobs; packs by layers during the forward: {packs}; registries (prep, pack) at the clears: {left}')
+    assert batches == [len(per_sample)]
+    assert not [p for p in packs if not p[2] and p[1] in k3]
+    assert left and left[0] == (0, 0)
+    assert torch.equal(got, want)

@@ -238,22 +238,44 @@ def test_winograd_launch_policy(monkeypatch):
     assert uw(3, 3, 1, 128, 128, pad=(1, 1), hw=(256, 256)) == 0
 
 
-def test_modconv16_policy_is_pure_host_logic():
-    """The form a 16-bit modulated convolution takes (training/networks._modconv16_policy: composite up = 2 kernels, one shared weight pack for the
-    batch where weights outweigh activations) is decided from shapes alone -- the layers and the stack's batched style preparation must agree on it."""
+def test_modconv16_policy_is_pure_host_logic(monkeypatch):
+    """The route a 16-bit modulated convolution takes (training/networks._modconv16_route: the form of an up = 2 layer, one shared weight pack for the
+    batch where weights outweigh activations) is decided from shapes alone, in one place -- the layers and the stack's batched preparation both read it."""
     import torch
     from training import networks as PN
     from torch_utils.ops import upfirdn2d
+    for name in ('PG_UP2_COMPOSITE', 'PG_UP2_POLICY', 'PG_UP2_MERGED_T_MIN', 'PG_UP2_FUSEDX', 'PG_UP2_FUSEDX_MIN', 'PG_UP2_MERGED', 'PG_MODCONV16_SHARED', 'PG_MODCONV16_SHARED_RATIO'):
+        monkeypatch.delenv(name, raising=False)
     f = upfirdn2d.setup_filter([1, 3, 3, 1])
-    comp, merged, shared, tpad, fir_pad, fused_x = PN._modconv16_policy((1024, 1024, 3, 3), (8, 8), 2, 1, f)
-    assert comp and not merged and not fused_x and shared and tuple(tpad) == (0, 0) and list(fir_pad) == [1, 1, 1, 1]      # 8^2: below the fused-x form's smallest image
-    comp, merged, shared, tpad, fir_pad, fused_x = PN._modconv16_policy((32, 64, 3, 3), (512, 512), 2, 1, f)
-    assert fused_x and not comp and not shared                 # round 5: the y half of the FIR in the weights, the x half in the epilogue; activations dominate: per-sample weights
-    comp, merged, shared, tpad, fir_pad, fused_x = PN._modconv16_policy((512, 1024, 3, 3), (32, 32), 2, 1, f)
-    assert fused_x and shared == (512 * 24 > 32 * 32)          # 24 tap slots per weight (18 non-zero); shared where the packed weights outweigh one sample's pixels (ratio 1 since round 5: +2 % on config 5)
-    assert PN._modconv16_policy((32, 64, 3, 3), (512, 512), 2, 1, upfirdn2d.setup_filter([1, 3, 3, 1]) + torch.eye(4) * 0.01)[5] is False      # not separable: composite
-    comp, merged, shared, tpad, fir_pad, fused_x = PN._modconv16_policy((512, 512, 3, 3), (64, 64), 1, 1, f)
-    assert not comp and not merged and not fused_x and shared == (512 * 9 > 64 * 64) and tpad is None
+    route = PN._modconv16_route
+    r = route((1024, 1024, 3, 3), (8, 8), 2, 1, f)
+    assert r.form == PN.R16_COMPOSITE and r.shared and tuple(r.tpad) == (0, 0) and list(r.fir_pad) == [1, 1, 1, 1]      # 8^2: below the fused-x form's smallest image
+    r = route((32, 64, 3, 3), (512, 512), 2, 1, f)
+    assert r.form == PN.R16_FUSED_X and not r.shared           # round 5: the y half of the FIR in the weights, the x half in the epilogue; activations dominate: per-sample weights
+    r = route((512, 1024, 3, 3), (32, 32), 2, 1, f)
+    assert r.form == PN.R16_FUSED_X and r.shared == (512 * 24 > 32 * 32)          # 24 tap slots per weight (18 non-zero); shared where the packed weights outweigh one sample's pixels (ratio 1 since round 5: +2 % on config 5)
+    assert route((32, 64, 3, 3), (512, 512), 2, 1, upfirdn2d.setup_filter([1, 3, 3, 1]) + torch.eye(4) * 0.01).form == PN.R16_COMPOSITE      # not separable: composite
+    r = route((512, 512, 3, 3), (64, 64), 1, 1, f)
+    assert r.form == PN.R16_UP1 and r.shared == (512 * 9 > 64 * 64) and r.tpad is None and r.fir_pad is None
+    # the composite as one four-phase launch or as four launches is part of the route: a Cout the four-phase launch does not cover, or PG_UP2_MERGED=0
+    assert route((48, 64, 3, 3), (16, 16), 2, 1, f).form == PN.R16_COMPOSITE_X4
+    monkeypatch.setenv('PG_UP2_MERGED', '0')
+    assert route((1024, 1024, 3, 3), (8, 8), 2, 1, f) == PN._Route16(PN.R16_COMPOSITE_X4, True, (0, 0), [1, 1, 1, 1])
+    monkeypatch.delenv('PG_UP2_MERGED')
+    # the two measured-and-not-adopted policies, and the switch between fused-x and the composite (read on every call)
+    monkeypatch.setenv('PG_UP2_FUSEDX', '0')
+    assert route((32, 64, 3, 3), (64, 64), 2, 1, f) == PN._Route16(PN.R16_COMPOSITE, 32 * 36 > 64 * 64, (0, 0), [1, 1, 1, 1])
+    monkeypatch.setenv('PG_UP2_POLICY', 'merged')
+    r = route((512, 1024, 3, 3), (32, 32), 2, 1, f)
+    assert r.form == PN.R16_MERGED_T and r.shared == (512 * 16 > 32 * 32)
+    assert route((1024, 1024, 3, 3), (16, 16), 2, 1, f).form == PN.R16_COMPOSITE           # merged-t starts at 32^2
+    monkeypatch.setenv('PG_UP2_POLICY', 'auto')
+    r = route((512, 1024, 3, 3), (32, 32), 2, 1, f)
+    assert r.form == PN.R16_TRANSPOSED and r.shared == (512 * 9 > 32 * 32)
+    assert route((32, 64, 3, 3), (512, 512), 2, 1, f).form == PN.R16_COMPOSITE           # 32 * 36 <= 2 * 512 * 512: activations dominate
+    monkeypatch.delenv('PG_UP2_POLICY')
+    monkeypatch.delenv('PG_UP2_FUSEDX')
+    assert route((64, 64, 3, 3), (16, 16), 2, 2, f).form == PN.R16_TRANSPOSED                # another padding: the transposed phases + FIR
     fy, fx = PN._separable_taps(f)
     assert torch.allclose(torch.outer(fy, fx), f) and PN._separable_taps(f) is PN._separable_taps(f)      # decided once per filter tensor
     assert PN._is_1331(f) and not PN._is_1331(upfirdn2d.setup_filter([1, 2, 1])) and not PN._is_1331(upfirdn2d.setup_filter([1, 3, 3, 1]) * 2)
