@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 15
+#define PG_ABI_VERSION 16
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -183,7 +183,7 @@ typedef struct pg_conv2d_fusion {
     /* Instance-norm statistics of the OUTPUT, gathered where it is produced (round 4): when set, every workgroup tile also writes the sum and M2
        (the sum of squared deviations from the tile's own mean; round 5, was the sum of squares) of its in-image outputs per output channel to stats_partial[((n * Cout + co) * T + t) * 2 + {0, 1}], T = the tile count of one
        image (pg_conv2d_winograd4_stats_tiles), t = the tile's index; pg_instance_norm_finish turns them into mean / rstd (fixed order: deterministic).
-       The values are those written to y (after the epilogue).  Only pg_conv2d_winograd4_forward launches with the plain tail (no in_scale, noise,
+       The values are those written to y (after the epilogue).  Only PG_WINO_F4 / PG_WINO_F4X3 launches of pg_conv2d_winograd_forward with the plain tail (no in_scale, noise,
        residual, SPADE) gather them; every other launch with this field set is declined (PG_ERR_UNSUPPORTED).  The SPADE res-blocks normalise the
        output of such a convolution (networks.py:1896-1904, 1715-1723): the separate statistics pass over it (pg_instance_norm_stats) is what this removes. */
     float*       stats_partial;
@@ -216,62 +216,39 @@ int pg_conv2d_forward_splitk(const float* x, const float* packed_w, float* y,
                              const pg_conv2d_fusion* fusion, float* workspace, int ksplit, void* stream);
 
 /*
- * Winograd F(2x2, 3x3) variant for KH = KW = 3, stride 1, out_step 1 (the bulk of the synthesis network): the same
- * result as pg_conv2d_forward up to fp32 summation order (~2e-6 of the output scale) with 2.25x fewer multiplies.
- * Weights are pre-transformed once (U = G g G^T, 16 * CinP * CoutP64 floats, CoutP64 = Cout rounded up to 64) by
- * pg_conv2d_winograd_pack_weight -- same scale / flip_hw / transpose_oi meaning as pg_conv2d_pack_weight.
- * Fusion: every stage of pg_conv2d_fusion except x2 (PG_ERR_UNSUPPORTED; use pg_conv2d_forward); SPADE mode uses
- * the same 32/32 gamma/beta row interleave as pg_conv2d_forward.  pad_x must be in [0, 4].
+ * Winograd forms of pg_conv2d_forward for KH = KW = 3, stride 1, out_step 1 (the bulk of the synthesis network): one entry set, `form` picks the kernel.
+ * Weights are pre-transformed once per weight version (U = G g G^T per (ci, co)) by pg_conv2d_winograd_pack_weight -- same scale / flip_hw / transpose_oi
+ * meaning as pg_conv2d_pack_weight -- into that form's operand stream of pg_conv2d_winograd_packed_size float32 units (CinP = Cin rounded up to 16,
+ * CoutP64 = Cout rounded up to 64; padded rows and channels are zero).  A form outside the enum: PG_ERR_INVALID_ARG (packed_size: 0), nothing launched.
+ *
+ *   PG_WINO_F2    F(2x2, 3x3), csrc/conv2d_wino.h: 16 * CinP * CoutP64 floats, transformed in float32.  The same result as pg_conv2d_forward up to fp32
+ *                 summation order (~2e-6 of the output scale) with 2.25x fewer multiplies.  Fusion: every stage of pg_conv2d_fusion except x2 and
+ *                 stats_partial; SPADE mode uses the same 32/32 gamma/beta row interleave as pg_conv2d_forward.
+ *   PG_WINO_F4    F(4x4, 3x3), one 12-wave workgroup per CU (round 3; csrc/conv2d_wino4.h): 2.25 multiplies per output instead of 4.  36 * CinP * CoutP64
+ *                 floats, transformed in float64 and rounded once.  float32 error ~4x that of F(2x2): max-abs 3.7e-5 on the config-2 image against the
+ *                 direct float32 network (tools/f43_error_probe.py).  Launches with the plain tail can gather stats_partial (below).
+ *   PG_WINO_F4B   the same algorithm with TWO workgroups per CU (round 4; csrc/conv2d_wino4b.h, v_mfma_f32_16x16x4_f32, 64 couts x 16 tiles per workgroup):
+ *                 the same 36 * CinP * CoutP64 values in its own stream order, bit-identical results.  SPADE combine mode expects gamma / beta rows packed as
+ *                 ADJACENT cout pairs (row 2c = gamma of channel c, row 2c + 1 = beta), not as blocks of 32.  No stats_partial.
+ *   PG_WINO_F4X3  the PG_WINO_F4 kernel with its transform-domain GEMM on the bf16 matrix pipe (round 6; csrc/conv2d_wino4.h, X3 form): every float32 operand
+ *                 of that GEMM is the exact sum of three bf16 values (truncation split, 8 + 8 + 8 significand bits) and the product is evaluated as the six
+ *                 largest of the nine plane products on v_mfma_f32_32x32x16_bf16 with float32 accumulation -- float32-class results (the three dropped
+ *                 products are below 2^-24 of the product), at 6/16 of the fp32 MFMA's issue time.  The PG_WINO_F4 values split into three 16-bit planes:
+ *                 54 * CinP * CoutP64 float32 units (6 bytes per transformed weight).  Fused stages and statistics as PG_WINO_F4.
+ *
+ * Every form declines x2 and a pad_x outside [0, 4] (PG_ERR_UNSUPPORTED; use pg_conv2d_forward).  The three F(4x4) forms also decline -- callers then use
+ * PG_WINO_F2 -- unless W % 4 == 0, x is 16-byte aligned, there is no input pre-activation stage (in_scale is supported), gain > 0 and an lrelu slope lies
+ * in [0, 1] (their tail evaluates the activation as a max), SPADE mode has no in_scale, and stats_partial comes with the plain tail only.
  */
-int64_t pg_conv2d_winograd_packed_size(int Cout, int Cin);
-int pg_conv2d_winograd_pack_weight(const float* w, float* packed, int Cout, int Cin,
+enum { PG_WINO_F2 = 1, PG_WINO_F4 = 2, PG_WINO_F4B = 3, PG_WINO_F4X3 = 4 };
+int64_t pg_conv2d_winograd_packed_size(int form, int Cout, int Cin);
+int pg_conv2d_winograd_pack_weight(int form, const float* w, float* packed, int Cout, int Cin,
                                    float scale, int flip_hw, int transpose_oi, void* stream);
-int pg_conv2d_winograd_forward(const float* x, const float* packed_u, float* y,
+int pg_conv2d_winograd_forward(int form, const float* x, const float* packed_u, float* y,
                                int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
                                const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream);
 
-/*
- * Winograd F(4x4, 3x3) variant (round 3; csrc/conv2d_wino4.h): 2.25 multiplies per output instead of 4 -- the same call
- * contract as the F(2x2) entry points above, its own weight layout (36 * CinP * CoutP64 floats, transformed in float64 and
- * rounded once).  Declines (PG_ERR_UNSUPPORTED; callers use pg_conv2d_winograd_forward) unless W % 4 == 0, x is 16-byte
- * aligned, pad_x in [0, 4], no x2 and no input pre-activation stage (in_scale is supported).  float32 error ~4x that of the
- * F(2x2) kernel: max-abs 3.7e-5 on the config-2 image against the direct float32 network (tools/f43_error_probe.py).
- */
-int64_t pg_conv2d_winograd4_packed_size(int Cout, int Cin);
-int pg_conv2d_winograd4_pack_weight(const float* w, float* packed, int Cout, int Cin,
-                                    float scale, int flip_hw, int transpose_oi, void* stream);
-int pg_conv2d_winograd4_forward(const float* x, const float* packed_u, float* y,
-                                int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
-                                const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream);
-
-/*
- * The same F(4x4, 3x3) algorithm with TWO workgroups per CU (round 4; csrc/conv2d_wino4b.h, v_mfma_f32_16x16x4_f32, 64 couts x 16
- * tiles per workgroup): same call contract, acceptance rules and numerics as pg_conv2d_winograd4_forward, its own weight stream
- * order (pg_conv2d_winograd4_packed_size floats).  SPADE combine mode expects gamma / beta rows packed as ADJACENT cout pairs
- * (row 2c = gamma of channel c, row 2c + 1 = beta), not as blocks of 32.
- */
-int pg_conv2d_winograd4b_pack_weight(const float* w, float* packed, int Cout, int Cin,
-                                     float scale, int flip_hw, int transpose_oi, void* stream);
-int pg_conv2d_winograd4b_forward(const float* x, const float* packed_u, float* y,
-                                 int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
-                                 const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream);
-
-/*
- * The F(4x4, 3x3) one-workgroup kernel with its transform-domain GEMM on the bf16 matrix pipe (round 6; csrc/conv2d_wino4.h, X3 form): every float32 operand
- * of that GEMM is the exact sum of three bf16 values (truncation split, 8 + 8 + 8 significand bits) and the product is evaluated as the six largest of the nine
- * plane products on v_mfma_f32_32x32x16_bf16 with float32 accumulation -- float32-class results (the three dropped products are below 2^-24 of the product),
- * at 6/16 of the fp32 MFMA's issue time.  The transformed weights are the float32 values of pg_conv2d_winograd4_pack_weight, split once per weight version:
- * pg_conv2d_winograd4x3_packed_size float32 units (6 bytes per transformed weight).  Same call contract, acceptance rules, fused stages and statistics as
- * pg_conv2d_winograd4_forward.
- */
-int64_t pg_conv2d_winograd4x3_packed_size(int Cout, int Cin);
-int pg_conv2d_winograd4x3_pack_weight(const float* w, float* packed, int Cout, int Cin,
-                                      float scale, int flip_hw, int transpose_oi, void* stream);
-int pg_conv2d_winograd4x3_forward(const float* x, const float* packed_u, float* y,
-                                  int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
-                                  const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream);
-
-/* Statistics gathered by pg_conv2d_winograd4_forward (pg_conv2d_fusion::stats_partial): tiles of one image for an OH x OW output, and the
+/* Statistics gathered by PG_WINO_F4 / PG_WINO_F4X3 launches (pg_conv2d_fusion::stats_partial): tiles of one image for an OH x OW output, and the
  * reduction of the per-tile (sum, M2) pairs into mean[n*C + c] and rstd = 1 / sqrt(var + eps) (biased variance over OH*OW): Chan's pairwise merge in
  * float64, tiles in index order per lane, then a fixed-shape wave reduction -- deterministic, and not E[x^2] - E[x]^2.  T = pg_conv2d_winograd4_stats_tiles(OH, OW). */
 int pg_conv2d_winograd4_stats_tiles(int OH, int OW);

@@ -34,7 +34,18 @@ __global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restric
     }
 }
 
-// Winograd F(2x2, 3x3) weight transform: U = G g G^T per (ci, co), stored in the operand-stream order of conv2d_wino.h.
+// ------------------------------------------------------------------ Winograd weight transforms (U = G g G^T per (ci, co), one thread each)
+// Element (ky, kx) of the 3x3 weight of (co, ci) as every Winograd packer reads it: OIHW or IOHW (`transpose_oi`) source, optionally flipped, scaled in
+// float32; zero beyond Cout / Cin (the padded rows and channels of the stream).
+__device__ __forceinline__ float wino_gather(const float* __restrict__ w, int co, int ci, int ky, int kx, int Cout, int Cin, float scale, int flip, int transpose_oi) {
+    if (co >= Cout || ci >= Cin) return 0.f;
+    const int sy = flip ? 2 - ky : ky, sx = flip ? 2 - kx : kx;
+    const int64_t src = transpose_oi ? (((int64_t)ci * Cout + co) * 3 + sy) * 3 + sx
+                                     : (((int64_t)co * Cin + ci) * 3 + sy) * 3 + sx;
+    return w[src] * scale;
+}
+
+// F(2x2, 3x3), float32 throughout, stored in the operand-stream order of conv2d_wino.h.
 //   G = [[1, 0, 0], [1/2, 1/2, 1/2], [1/2, -1/2, 1/2], [0, 0, 1]]
 __global__ __launch_bounds__(256) void wino_pack_kernel(const float* __restrict__ w, float* __restrict__ up, int Cout, int Cin,
                                                         int CinP, int CoutP, float scale, int flip, int transpose_oi) {
@@ -45,16 +56,7 @@ __global__ __launch_bounds__(256) void wino_pack_kernel(const float* __restrict_
 #pragma unroll
         for (int ky = 0; ky < 3; ky++)
 #pragma unroll
-            for (int kx = 0; kx < 3; kx++) {
-                float v = 0.f;
-                if (co < Cout && ci < Cin) {
-                    const int sy = flip ? 2 - ky : ky, sx = flip ? 2 - kx : kx;
-                    const int64_t src = transpose_oi ? (((int64_t)ci * Cout + co) * 3 + sy) * 3 + sx
-                                                     : (((int64_t)co * Cin + ci) * 3 + sy) * 3 + sx;
-                    v = w[src] * scale;
-                }
-                g[ky][kx] = v;
-            }
+            for (int kx = 0; kx < 3; kx++) g[ky][kx] = wino_gather(w, co, ci, ky, kx, Cout, Cin, scale, flip, transpose_oi);
         float t[4][3];                                   // G g
 #pragma unroll
         for (int kx = 0; kx < 3; kx++) {
@@ -76,12 +78,49 @@ __global__ __launch_bounds__(256) void wino_pack_kernel(const float* __restrict_
     }
 }
 
-
-// Winograd F(4x4, 3x3) weight transform: U = G g G^T (6x6) per (ci, co) in float64, rounded once, stored in the order the waves of
-// conv2d_wino4.h walk it: [m-block 64][mt][a][chunk 16 ch][group = (b half jg, pair quad)][b third jj][lane = (h, co & 31)][pair s], with
-//   xi = 6a + b,  b = 3jg + jj,   channel = 16 chunk + 2 (4 quad + s) + h.
+// F(4x4, 3x3): the 6x6 U in float64, rounded to float32 ONCE; where element xi = 6a + b of (co, ci) goes, and in what form, is the layout's business -- one
+// struct per kernel form (PG_WINO_F4 / F4B / F4X3 of pasta_gan_ops.h), in the order that form's waves walk the stream (nchunks = CinP / 16).
 //   G = [[1/4, 0, 0], [-1/6, -1/6, -1/6], [-1/6, 1/6, -1/6], [1/24, 1/12, 1/6], [1/24, -1/12, 1/6], [0, 0, 1]]
-__global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict__ w, float* __restrict__ up, int Cout, int Cin,
+struct Wino4PackF4 {       // conv2d_wino4.h: [m-block 64][mt][a][chunk 16 ch][group = (b half jg, pair quad)][b third jj][lane = (h, co & 31)][pair s]
+    typedef float word;    //   with b = 3jg + jj,   channel = 16 chunk + 2 (4 quad + s) + h
+    static __device__ __forceinline__ void store(float* __restrict__ up, int co, int ci, int a, int b, int nchunks, double u) {
+        const int mb = co >> 6, mt = (co >> 5) & 1, m = co & 31;
+        const int k = ci >> 4, cc = ci & 15, pair = cc >> 1, h = cc & 1, quad = pair >> 2, sp = pair & 3;
+        const int jg = b / 3, jj = b % 3;
+        const int64_t unit = ((int64_t)(mb * 2 + mt) * 6 + a) * nchunks + k;
+        up[((((unit * 2 + jg) * 2 + quad) * 3 + jj) * 64 + (h * 32 + m)) * 4 + sp] = (float)u;
+    }
+};
+struct Wino4PackF4B {      // conv2d_wino4b.h (v_mfma_f32_16x16x4_f32): [m-block 64][cout block cb 4][row half ah 2][chunk 16 ch][e = 6 a' + b (18)][lane = (kq, m) 64][j 4]
+    typedef float word;    //   with a = 3 ah + a', cout = 64 mb + 16 cb + m, channel = 16 chunk + 4 j + kq: one 16-byte word per lane = the A operands of the four K steps of one xi
+    static __device__ __forceinline__ void store(float* __restrict__ up, int co, int ci, int a, int b, int nchunks, double u) {
+        const int mb = co >> 6, cbk = (co >> 4) & 3, m = co & 15;
+        const int k = ci >> 4, cc = ci & 15, j = cc >> 2, kq = cc & 3;
+        const int64_t unit = ((int64_t)(mb * 4 + cbk) * 2 + a / 3) * nchunks + k;
+        up[((unit * 18 + (a % 3) * 6 + b) * 64 + (kq * 16 + m)) * 4 + j] = (float)u;
+    }
+};
+struct Wino4PackF4X3 {     // X3 form of conv2d_wino4.h: the float32 value the fp32 form multiplies by, split exactly into three bf16 planes by truncation (u = p0 + p1 + p2,
+    typedef unsigned short word;   // 8 + 8 + 8 significand bits), stored [m-block 64][mt][a][chunk 16 ch][b 6][plane 3][lane = (h, co & 31)][j 8] as 16-bit words with
+                                   // channel = 16 chunk + 2 j + h: one 16-byte word per lane = the A operand of one v_mfma_f32_32x32x16_bf16
+    static __device__ __forceinline__ void store(unsigned short* __restrict__ up, int co, int ci, int a, int b, int nchunks, double ud) {
+        const int mb = co >> 6, mt = (co >> 5) & 1, m = co & 31;
+        const int k = ci >> 4, cc = ci & 15, j = cc >> 1, h = cc & 1;
+        const float u = (float)ud;
+        const unsigned u0 = __float_as_uint(u) & 0xffff0000u;
+        const float r = u - __uint_as_float(u0);
+        const unsigned u1 = __float_as_uint(r) & 0xffff0000u;
+        const unsigned u2 = __float_as_uint(r - __uint_as_float(u1)) & 0xffff0000u;
+        const int64_t unit = ((int64_t)(mb * 2 + mt) * 6 + a) * nchunks + k;
+        const int64_t dst = (((unit * 6 + b) * 3) * 64 + (h * 32 + m)) * 8 + j;                     // plane 0; planes are 64 * 8 words apart
+        up[dst] = (unsigned short)(u0 >> 16);
+        up[dst + 512] = (unsigned short)(u1 >> 16);
+        up[dst + 1024] = (unsigned short)(u2 >> 16);
+    }
+};
+
+template <class Layout>
+__global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict__ w, typename Layout::word* __restrict__ up, int Cout, int Cin,
                                                          int CinP, int CoutP, float scale, int flip, int transpose_oi) {
     const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                             {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
@@ -93,127 +132,17 @@ __global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict
 #pragma unroll
         for (int ky = 0; ky < 3; ky++)
 #pragma unroll
-            for (int kx = 0; kx < 3; kx++) {
-                double v = 0.0;
-                if (co < Cout && ci < Cin) {
-                    const int sy = flip ? 2 - ky : ky, sx = flip ? 2 - kx : kx;
-                    const int64_t src = transpose_oi ? (((int64_t)ci * Cout + co) * 3 + sy) * 3 + sx
-                                                     : (((int64_t)co * Cin + ci) * 3 + sy) * 3 + sx;
-                    v = (double)(w[src] * scale);
-                }
-                g[ky][kx] = v;
-            }
+            for (int kx = 0; kx < 3; kx++) g[ky][kx] = (double)wino_gather(w, co, ci, ky, kx, Cout, Cin, scale, flip, transpose_oi);
         double tg[6][3];                                 // G g
 #pragma unroll
         for (int a = 0; a < 6; a++)
 #pragma unroll
             for (int kx = 0; kx < 3; kx++) tg[a][kx] = G[a][0] * g[0][kx] + G[a][1] * g[1][kx] + G[a][2] * g[2][kx];
-        const int mb = co >> 6, mt = (co >> 5) & 1, m = co & 31;
-        const int k = ci >> 4, cc = ci & 15, pair = cc >> 1, h = cc & 1, quad = pair >> 2, sp = pair & 3;
 #pragma unroll
         for (int a = 0; a < 6; a++)
 #pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const double u = tg[a][0] * G[b][0] + tg[a][1] * G[b][1] + tg[a][2] * G[b][2];      // (G g) G^T
-                const int jg = b / 3, jj = b % 3;
-                const int64_t unit = ((int64_t)(mb * 2 + mt) * 6 + a) * nchunks + k;
-                const int64_t dst = ((((unit * 2 + jg) * 2 + quad) * 3 + jj) * 64 + (h * 32 + m)) * 4 + sp;
-                up[dst] = (float)u;
-            }
-    }
-}
-
-// The same transform for the X3 form of conv2d_wino4.h: U rounded to float32 once (the value the fp32 form multiplies by), then split exactly into three bf16
-// planes by truncation (u = p0 + p1 + p2, 8 + 8 + 8 significand bits), stored [m-block 64][mt][a][chunk 16 ch][b 6][plane 3][lane = (h, co & 31)][j 8] as 16-bit
-// words with channel = 16 chunk + 2 j + h: one 16-byte word per lane = the A operand of one v_mfma_f32_32x32x16_bf16.
-__global__ __launch_bounds__(256) void wino4x3_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ up, int Cout, int Cin,
-                                                           int CinP, int CoutP, float scale, int flip, int transpose_oi) {
-    const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
-    const int nchunks = CinP / 16;
-    const int64_t total = (int64_t)CinP * CoutP;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int co = (int)(i % CoutP), ci = (int)(i / CoutP);
-        double g[3][3];
-#pragma unroll
-        for (int ky = 0; ky < 3; ky++)
-#pragma unroll
-            for (int kx = 0; kx < 3; kx++) {
-                double v = 0.0;
-                if (co < Cout && ci < Cin) {
-                    const int sy = flip ? 2 - ky : ky, sx = flip ? 2 - kx : kx;
-                    const int64_t src = transpose_oi ? (((int64_t)ci * Cout + co) * 3 + sy) * 3 + sx
-                                                     : (((int64_t)co * Cin + ci) * 3 + sy) * 3 + sx;
-                    v = (double)(w[src] * scale);
-                }
-                g[ky][kx] = v;
-            }
-        double tg[6][3];                                 // G g
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int kx = 0; kx < 3; kx++) tg[a][kx] = G[a][0] * g[0][kx] + G[a][1] * g[1][kx] + G[a][2] * g[2][kx];
-        const int mb = co >> 6, mt = (co >> 5) & 1, m = co & 31;
-        const int k = ci >> 4, cc = ci & 15, j = cc >> 1, h = cc & 1;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const float u = (float)(tg[a][0] * G[b][0] + tg[a][1] * G[b][1] + tg[a][2] * G[b][2]);      // (G g) G^T, rounded once
-                const unsigned u0 = __float_as_uint(u) & 0xffff0000u;
-                const float r = u - __uint_as_float(u0);
-                const unsigned u1 = __float_as_uint(r) & 0xffff0000u;
-                const unsigned u2 = __float_as_uint(r - __uint_as_float(u1)) & 0xffff0000u;
-                const int64_t unit = ((int64_t)(mb * 2 + mt) * 6 + a) * nchunks + k;
-                const int64_t dst = (((unit * 6 + b) * 3) * 64 + (h * 32 + m)) * 8 + j;                     // plane 0; planes are 64 * 8 words apart
-                up[dst] = (unsigned short)(u0 >> 16);
-                up[dst + 512] = (unsigned short)(u1 >> 16);
-                up[dst + 1024] = (unsigned short)(u2 >> 16);
-            }
-    }
-}
-
-// The same transform in the order the waves of conv2d_wino4b.h walk it (two workgroups per CU, v_mfma_f32_16x16x4_f32):
-//   [m-block 64][cout block cb 4][row half ah 2][chunk 16 ch][e = 6 a' + b (18)][lane = (kq, m) 64][j 4]
-//   with xi = 6 (3 ah + a') + b, cout = 64 mb + 16 cb + m, channel = 16 chunk + 4 j + kq: one 16-byte word per lane = the A operands of the four K steps of one xi.
-__global__ __launch_bounds__(256) void wino4b_pack_kernel(const float* __restrict__ w, float* __restrict__ up, int Cout, int Cin,
-                                                          int CinP, int CoutP, float scale, int flip, int transpose_oi) {
-    const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                            {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
-    const int nchunks = CinP / 16;
-    const int64_t total = (int64_t)CinP * CoutP;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int co = (int)(i % CoutP), ci = (int)(i / CoutP);
-        double g[3][3];
-#pragma unroll
-        for (int ky = 0; ky < 3; ky++)
-#pragma unroll
-            for (int kx = 0; kx < 3; kx++) {
-                double v = 0.0;
-                if (co < Cout && ci < Cin) {
-                    const int sy = flip ? 2 - ky : ky, sx = flip ? 2 - kx : kx;
-                    const int64_t src = transpose_oi ? (((int64_t)ci * Cout + co) * 3 + sy) * 3 + sx
-                                                     : (((int64_t)co * Cin + ci) * 3 + sy) * 3 + sx;
-                    v = (double)(w[src] * scale);
-                }
-                g[ky][kx] = v;
-            }
-        double tg[6][3];                                 // G g
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int kx = 0; kx < 3; kx++) tg[a][kx] = G[a][0] * g[0][kx] + G[a][1] * g[1][kx] + G[a][2] * g[2][kx];
-        const int mb = co >> 6, cbk = (co >> 4) & 3, m = co & 15;
-        const int k = ci >> 4, cc = ci & 15, j = cc >> 2, kq = cc & 3;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const double u = tg[a][0] * G[b][0] + tg[a][1] * G[b][1] + tg[a][2] * G[b][2];      // (G g) G^T
-                const int64_t unit = ((int64_t)(mb * 4 + cbk) * 2 + a / 3) * nchunks + k;
-                const int64_t dst = ((unit * 18 + (a % 3) * 6 + b) * 64 + (kq * 16 + m)) * 4 + j;
-                up[dst] = (float)u;
-            }
+            for (int b = 0; b < 6; b++)
+                Layout::store(up, co, ci, a, b, nchunks, tg[a][0] * G[b][0] + tg[a][1] * G[b][1] + tg[a][2] * G[b][2]);      // (G g) G^T
     }
 }
 
@@ -656,7 +585,8 @@ PG_EXPORT int pg_conv2d_pack_weight(const float* w, float* packed, int Cout, int
     return pg::launch_status();
 }
 
-static int conv_forward(int winograd, const float* x, const float* packed_w, float* y,
+// form: 0 = the direct implicit GEMM, otherwise a PG_WINO_* form of the 3x3 stride-1 convolution
+static int conv_forward(int form, const float* x, const float* packed_w, float* y,
                         int N, int Cin, int H, int W, int Cout, int KH, int KW,
                         int stride, int pad_y, int pad_x, int OH, int OW,
                         const int64_t ystride[4], int out_step_y, int out_step_x, int out_off_y, int out_off_x,
@@ -703,12 +633,18 @@ static int conv_forward(int winograd, const float* x, const float* packed_w, flo
     if (p.in_xform && (!(p.f.in_gain > 0.f) || p.f.in_alpha < 0.f || p.f.in_alpha > 1.f)) return PG_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
 
-    if (p.f.stats_partial && winograd != 2 && winograd != 4) return PG_ERR_UNSUPPORTED;      // output statistics: the F(4x4) one-workgroup kernel's plain tail only
-    if (winograd) {
+    if (p.f.stats_partial && form != PG_WINO_F4 && form != PG_WINO_F4X3) return PG_ERR_UNSUPPORTED;      // output statistics: the F(4x4) one-workgroup kernel's plain tail only
+    if (form) {
         if (p.f.x2) return PG_ERR_UNSUPPORTED;                  // two-source launches stay on the direct kernel
         if (pad_x < 0 || pad_x > 4) return PG_ERR_UNSUPPORTED;  // the LDS halo row starts 4 columns left of the tile
         p.CoutP = round_up(Cout, 64);
-        return winograd == 4 ? pgconv::launch_wino4x3(p, s) : winograd == 3 ? pgconv::launch_wino4b(p, s) : winograd == 2 ? pgconv::launch_wino4(p, s) : pgconv::launch_wino(p, s);
+        switch (form) {
+        case PG_WINO_F2:   return pgconv::launch_wino(p, s);
+        case PG_WINO_F4:   return pgconv::launch_wino4(p, s);
+        case PG_WINO_F4B:  return pgconv::launch_wino4b(p, s);
+        case PG_WINO_F4X3: return pgconv::launch_wino4x3(p, s);
+        }
+        return PG_ERR_INVALID_ARG;
     }
     pg_conv2d_fusion tail = p.f;
     const int64_t slice = (int64_t)N * Cout * OH * OW;
@@ -778,87 +714,36 @@ PG_EXPORT int pg_conv2d_forward_splitk(const float* x, const float* packed_w, fl
                         ystride, out_step_y, out_step_x, out_off_y, out_off_x, fusion, stream, workspace, ksplit);
 }
 
-PG_EXPORT int64_t pg_conv2d_winograd_packed_size(int Cout, int Cin) {
-    if (Cout <= 0 || Cin <= 0) return 0;
-    return (int64_t)16 * round_up(Cin, 16) * round_up(Cout, 64);
+// The Winograd forms of the 3x3 stride-1 convolution (PG_WINO_* of pasta_gan_ops.h): one entry set, the form is an argument.
+PG_EXPORT int64_t pg_conv2d_winograd_packed_size(int form, int Cout, int Cin) {
+    static const int per_weight[] = {0, 16, 36, 36, 54};      // float32 units per (ci, co): 4x4, 6x6, 6x6, 6x6 as three 16-bit planes
+    if (form < PG_WINO_F2 || form > PG_WINO_F4X3 || Cout <= 0 || Cin <= 0) return 0;
+    return (int64_t)per_weight[form] * round_up(Cin, 16) * round_up(Cout, 64);
 }
 
-PG_EXPORT int pg_conv2d_winograd_pack_weight(const float* w, float* packed, int Cout, int Cin,
+PG_EXPORT int pg_conv2d_winograd_pack_weight(int form, const float* w, float* packed, int Cout, int Cin,
                                              float scale, int flip_hw, int transpose_oi, void* stream) {
-    if (!w || !packed || Cout <= 0 || Cin <= 0) return PG_ERR_INVALID_ARG;
+    if (form < PG_WINO_F2 || form > PG_WINO_F4X3 || !w || !packed || Cout <= 0 || Cin <= 0) return PG_ERR_INVALID_ARG;
     const int CinP = round_up(Cin, 16), CoutP = round_up(Cout, 64);
     const int64_t total = (int64_t)CinP * CoutP;
     int64_t blocks = (total + 255) / 256;
     if (blocks > pg::max_stream_blocks()) blocks = pg::max_stream_blocks();
-    hipLaunchKernelGGL(wino_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi);
+    const dim3 grid((unsigned)blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (form) {
+    case PG_WINO_F2:   hipLaunchKernelGGL(wino_pack_kernel, grid, block, 0, s, w, packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi); break;
+    case PG_WINO_F4:   hipLaunchKernelGGL(wino4_pack_kernel<Wino4PackF4>, grid, block, 0, s, w, packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi); break;
+    case PG_WINO_F4B:  hipLaunchKernelGGL(wino4_pack_kernel<Wino4PackF4B>, grid, block, 0, s, w, packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi); break;
+    case PG_WINO_F4X3: hipLaunchKernelGGL(wino4_pack_kernel<Wino4PackF4X3>, grid, block, 0, s, w, (unsigned short*)packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi); break;
+    }
     return pg::launch_status();
 }
 
-PG_EXPORT int pg_conv2d_winograd_forward(const float* x, const float* packed_u, float* y,
+PG_EXPORT int pg_conv2d_winograd_forward(int form, const float* x, const float* packed_u, float* y,
                                          int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
                                          const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream) {
-    return conv_forward(1, x, packed_u, y, N, Cin, H, W, Cout, 3, 3, 1, pad_y, pad_x, OH, OW, ystride, 1, 1, 0, 0, fusion, stream);
-}
-
-PG_EXPORT int64_t pg_conv2d_winograd4_packed_size(int Cout, int Cin) {
-    if (Cout <= 0 || Cin <= 0) return 0;
-    return (int64_t)36 * round_up(Cin, 16) * round_up(Cout, 64);
-}
-
-PG_EXPORT int pg_conv2d_winograd4_pack_weight(const float* w, float* packed, int Cout, int Cin,
-                                              float scale, int flip_hw, int transpose_oi, void* stream) {
-    if (!w || !packed || Cout <= 0 || Cin <= 0) return PG_ERR_INVALID_ARG;
-    const int CinP = round_up(Cin, 16), CoutP = round_up(Cout, 64);
-    const int64_t total = (int64_t)CinP * CoutP;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > pg::max_stream_blocks()) blocks = pg::max_stream_blocks();
-    hipLaunchKernelGGL(wino4_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi);
-    return pg::launch_status();
-}
-
-PG_EXPORT int pg_conv2d_winograd4_forward(const float* x, const float* packed_u, float* y,
-                                          int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
-                                          const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream) {
-    return conv_forward(2, x, packed_u, y, N, Cin, H, W, Cout, 3, 3, 1, pad_y, pad_x, OH, OW, ystride, 1, 1, 0, 0, fusion, stream);
-}
-
-PG_EXPORT int64_t pg_conv2d_winograd4x3_packed_size(int Cout, int Cin) {      // in float32 units (6 bytes per transformed weight)
-    if (Cout <= 0 || Cin <= 0) return 0;
-    return (int64_t)54 * round_up(Cin, 16) * round_up(Cout, 64);
-}
-
-PG_EXPORT int pg_conv2d_winograd4x3_pack_weight(const float* w, float* packed, int Cout, int Cin,
-                                                float scale, int flip_hw, int transpose_oi, void* stream) {
-    if (!w || !packed || Cout <= 0 || Cin <= 0) return PG_ERR_INVALID_ARG;
-    const int CinP = round_up(Cin, 16), CoutP = round_up(Cout, 64);
-    const int64_t total = (int64_t)CinP * CoutP;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > pg::max_stream_blocks()) blocks = pg::max_stream_blocks();
-    hipLaunchKernelGGL(wino4x3_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi);
-    return pg::launch_status();
-}
-
-PG_EXPORT int pg_conv2d_winograd4x3_forward(const float* x, const float* packed_u, float* y,
-                                            int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
-                                            const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream) {
-    return conv_forward(4, x, packed_u, y, N, Cin, H, W, Cout, 3, 3, 1, pad_y, pad_x, OH, OW, ystride, 1, 1, 0, 0, fusion, stream);
-}
-
-PG_EXPORT int pg_conv2d_winograd4b_pack_weight(const float* w, float* packed, int Cout, int Cin,
-                                               float scale, int flip_hw, int transpose_oi, void* stream) {
-    if (!w || !packed || Cout <= 0 || Cin <= 0) return PG_ERR_INVALID_ARG;
-    const int CinP = round_up(Cin, 16), CoutP = round_up(Cout, 64);
-    const int64_t total = (int64_t)CinP * CoutP;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > pg::max_stream_blocks()) blocks = pg::max_stream_blocks();
-    hipLaunchKernelGGL(wino4b_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin, CinP, CoutP, scale, flip_hw, transpose_oi);
-    return pg::launch_status();
-}
-
-PG_EXPORT int pg_conv2d_winograd4b_forward(const float* x, const float* packed_u, float* y,
-                                           int N, int Cin, int H, int W, int Cout, int pad_y, int pad_x, int OH, int OW,
-                                           const int64_t ystride[4], const pg_conv2d_fusion* fusion, void* stream) {
-    return conv_forward(3, x, packed_u, y, N, Cin, H, W, Cout, 3, 3, 1, pad_y, pad_x, OH, OW, ystride, 1, 1, 0, 0, fusion, stream);
+    if (form < PG_WINO_F2 || form > PG_WINO_F4X3) return PG_ERR_INVALID_ARG;
+    return conv_forward(form, x, packed_u, y, N, Cin, H, W, Cout, 3, 3, 1, pad_y, pad_x, OH, OW, ystride, 1, 1, 0, 0, fusion, stream);
 }
 
 // Streaming 1x1 head for fp32 NCHW tensors (the ToRGB / parsing heads: Cout <= 8, networks.py:287-316): a thread owns 4 adjacent

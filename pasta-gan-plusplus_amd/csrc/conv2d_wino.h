@@ -15,7 +15,7 @@
 //     pipe.  The tile arrives by 16-byte LDS-DMA (`buffer_load_dwordx4 ... lds`; zero padding = the buffer range check
 //     on a per-lane sentinel offset), double buffered, one barrier per 16 channels.  Ragged widths (W % 4 != 0) use the
 //     4-byte DMA form of the same map.
-//   * A operand (U = G g G^T, pre-transformed by pg_conv2d_winograd_pack_weight) is used by exactly one wave, so it is
+//   * A operand (U = G g G^T, pre-transformed by pg_conv2d_winograd_pack_weight(PG_WINO_F2)) is used by exactly one wave, so it is
 //     NOT staged in LDS: the packed order [a][co/32][ci/2][ci&1][co&31][b] makes the four b values of a lane one 16-byte
 //     word and every wave-instruction a contiguous 1 KB; each wave streams its slice from L2 through a 4-pair ring.
 //   * vector-memory instructions are the scarce resource of this kernel (the texture-address path takes ~16 cycles per

@@ -17,7 +17,7 @@
 //   * GEMM phase: wave w = (a = w >> 1, mt = w & 1) owns row a of the 6x6 transform domain, xi = 6a .. 6a + 5, for cout M-tile mt:
 //     6 accumulators = 96 VGPRs.  Per chunk 48 MFMAs per wave in four groups of (3 xi) x (4 channel pairs): three accumulators in
 //     rotation; a group's A words are three 16-byte loads (1 KB per wave-instruction, 3 KB contiguous per group, packed by
-//     pg_conv2d_winograd4_pack_weight in exactly the order the wave walks), its B words six ds_read2st64_b32 of V.
+//     pg_conv2d_winograd_pack_weight(PG_WINO_F4) in exactly the order the wave walks), its B words six ds_read2st64_b32 of V.
 //   * transform phase: waves 0-7 (16 channels x 32 tiles, one 6x6 patch per thread); waves 8-11 own the chores instead: they issue
 //     the 16-byte LDS-DMA of the raw 10-row halo tile [16][10][72] for chunk k+1 as soon as the transform of chunk k is done (gather
 //     map kept in LDS; zero padding = the buffer range check on a sentinel offset), compute edge-tile gather maps and fetch the
@@ -144,7 +144,7 @@ __device__ __forceinline__ int w4_fresh_lane() {
 //   W4_TAIL_RES / W4_TAIL_NOISE (residual only / noise only) compile cleanly too but measured +1 % / -1 ... +5 %: not instantiated.
 enum { W4_TAIL_ANY = 0, W4_TAIL_PLAIN = 1, W4_TAIL_SPADE = 2, W4_TAIL_RES = 3, W4_TAIL_NOISE = 4, W4_TAIL_STATS = 5 };
 // X3 (round 6): the Winograd-domain GEMM on v_mfma_f32_32x32x16_bf16 as six products of exact three-term operand splits (fp32 accumulation): U is split once per
-// weight version by pg_conv2d_winograd4x3_pack_weight, the V values a lane reads from LDS are split in registers by the multiplying wave itself -- LDS keeps the
+// weight version by pg_conv2d_winograd_pack_weight(PG_WINO_F4X3), the V values a lane reads from LDS are split in registers by the multiplying wave itself -- LDS keeps the
 // float32 V, the transform phase and the tail are the fp32 form's.  Per (xi, 16-channel chunk): 44 VALU + 6 MFMAs of 32 cycles instead of 8 MFMAs of 64 cycles;
 // the vector work of one wave runs beside the matrix work of the other two waves of its SIMD.
 template <int MODE, int TAIL, bool X3 = false>
@@ -865,6 +865,21 @@ int launch_wino4_mode(const ConvParams& p0, hipStream_t s) {
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((conv2d_wino4<MODE, TAIL, X3>), dim3((unsigned)blocks), dim3(768), lds, s, p);
     return launch_status();
+}
+
+// The acceptance rules of the F(4x4) family -- the fp32, two-workgroup and X3 forms share the staging and the tail arithmetic these rules protect, so their
+// dispatchers (conv2d_inst_wino4.hip, conv2d_inst_wino4b.hip, conv2d_inst_wino4x.hip) all ask here and keep only their choice of instantiation.  A declined
+// launch (PG_ERR_UNSUPPORTED) runs on F(2x2) / the direct kernel; `use_winograd` of conv2d_mfma.py mirrors these rules.  `has_stats_tail`: whether the form
+// has a W4_TAIL_STATS instantiation (the two-workgroup form has none).
+inline bool wino4_declines(const ConvParams& p, bool has_stats_tail) {
+    // 16-byte halo DMA and 16-byte patch reads: every 4-column word of a row is inside or outside the image as a whole
+    if (p.W % 4 != 0 || (((uintptr_t)p.x) & 15) != 0 || p.in_xform || p.f.x2 || p.pad_x < 0 || p.pad_x > 4) return true;
+    // the tail's activation is max(v * gain, v * gain * slope): exact only for gain > 0 and a slope in [0, 1] -- anything else
+    // runs on F(2x2) / the direct kernel, whose tails use the select form
+    if (!(p.f.gain > 0.f) || (p.f.act == PG_ACT_LRELU && !(p.f.alpha >= 0.f && p.f.alpha <= 1.f))) return true;
+    // output statistics: plain tail only
+    if (p.f.stats_partial && (!has_stats_tail || p.f.spade_x || p.f.in_scale || p.f.residual || p.f.noise)) return true;
+    return p.f.spade_x && p.f.in_scale;      // no modulated SPADE combine
 }
 
 }  // namespace pgconv

@@ -52,7 +52,7 @@ PLUGIN_SOURCES = {
                       'conv2d16_inst_k1x2.hip', 'conv2d16_inst_k3s2.hip', 'conv2d16_inst_up2f.hip', 'conv1x1_head16.hip', 'conv1x1_fold.hip', 'optim.hip'],
 }
 
-ABI_VERSION = 15     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
+ABI_VERSION = 16     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
 
 _cached_plugins = dict()
 

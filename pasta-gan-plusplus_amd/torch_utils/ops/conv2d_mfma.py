@@ -95,31 +95,15 @@ def _init(plugin_name='conv2d_plugin'):
         lib.pg_conv2d_forward_splitk.restype = i
         lib.pg_conv2d_forward_splitk.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, i, ctypes.POINTER(i64), i, i, i, i, ctypes.POINTER(Fusion), vp, i, vp]
         lib.pg_conv2d_winograd_packed_size.restype = i64
-        lib.pg_conv2d_winograd_packed_size.argtypes = [i, i]
+        lib.pg_conv2d_winograd_packed_size.argtypes = [i, i, i]
         lib.pg_conv2d_winograd_pack_weight.restype = i
-        lib.pg_conv2d_winograd_pack_weight.argtypes = [vp, vp, i, i, f, i, i, vp]
+        lib.pg_conv2d_winograd_pack_weight.argtypes = [i, vp, vp, i, i, f, i, i, vp]
         lib.pg_conv2d_winograd_forward.restype = i
-        lib.pg_conv2d_winograd_forward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, i, ctypes.POINTER(i64), ctypes.POINTER(Fusion), vp]
-        lib.pg_conv2d_winograd4_packed_size.restype = i64
-        lib.pg_conv2d_winograd4_packed_size.argtypes = [i, i]
-        lib.pg_conv2d_winograd4_pack_weight.restype = i
-        lib.pg_conv2d_winograd4_pack_weight.argtypes = [vp, vp, i, i, f, i, i, vp]
-        lib.pg_conv2d_winograd4_forward.restype = i
-        lib.pg_conv2d_winograd4_forward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, i, ctypes.POINTER(i64), ctypes.POINTER(Fusion), vp]
-        lib.pg_conv2d_winograd4x3_packed_size.restype = i64
-        lib.pg_conv2d_winograd4x3_packed_size.argtypes = [i, i]
-        lib.pg_conv2d_winograd4x3_pack_weight.restype = i
-        lib.pg_conv2d_winograd4x3_pack_weight.argtypes = [vp, vp, i, i, f, i, i, vp]
-        lib.pg_conv2d_winograd4x3_forward.restype = i
-        lib.pg_conv2d_winograd4x3_forward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, i, ctypes.POINTER(i64), ctypes.POINTER(Fusion), vp]
+        lib.pg_conv2d_winograd_forward.argtypes = [i, vp, vp, vp, i, i, i, i, i, i, i, i, i, ctypes.POINTER(i64), ctypes.POINTER(Fusion), vp]
         lib.pg_conv2d_winograd4_stats_tiles.restype = i
         lib.pg_conv2d_winograd4_stats_tiles.argtypes = [i, i]
         lib.pg_instance_norm_finish.restype = i
         lib.pg_instance_norm_finish.argtypes = [vp, vp, vp, i, i, i, i, f, vp]
-        lib.pg_conv2d_winograd4b_pack_weight.restype = i
-        lib.pg_conv2d_winograd4b_pack_weight.argtypes = [vp, vp, i, i, f, i, i, vp]
-        lib.pg_conv2d_winograd4b_forward.restype = i
-        lib.pg_conv2d_winograd4b_forward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, i, ctypes.POINTER(i64), ctypes.POINTER(Fusion), vp]
         lib.pg_spade_masked_sums.restype = i
         lib.pg_spade_masked_sums.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
         lib.pg_spade_feat_assemble.restype = i
@@ -180,28 +164,45 @@ def _init(plugin_name='conv2d_plugin'):
     return _plugin
 
 
-# Which F(4x4,3x3) kernel the policy hands out: 2 = csrc/conv2d_wino4.h (one 12-wave workgroup per CU, 8 x 64-pixel tiles, round 3), 3 = csrc/conv2d_wino4b.h
+# The Winograd forms of the 3x3 stride-1 convolution: the values of PG_WINO_* in include/pasta_gan_ops.h, what `use_winograd` returns and what the `winograd=`
+# keyword of `pack_weight` / `conv2d_forward` / `pack_spade_gamma_beta` takes (True = WINO_F2, False / 0 = the direct kernel).
+WINO_F2, WINO_F4, WINO_F4B, WINO_F4X3 = 1, 2, 3, 4
+# Everything this module decides per form, once: (the timeline's algorithm key -- bench.py's roofline table is keyed on it; the form has a statistics tail
+# (`stats_eps`); its SPADE tail wants gamma / beta of a channel as ADJACENT rows instead of blocks of 32).  Form 0 = the direct kernel.
+WINO_FORMS = {0: ('direct', False, False), WINO_F2: ('winograd', False, False), WINO_F4: ('winograd4', True, False),
+              WINO_F4B: ('winograd4', False, True), WINO_F4X3: ('winograd4x3', True, False)}
+
+
+def _wino_form(winograd):
+    """The `winograd=` keyword as (form, timeline label, has_stats_tail, spade_pairs)."""
+    if int(winograd) not in WINO_FORMS:
+        raise nat.NativeOpError(f'conv2d_mfma: winograd={winograd!r} is not one of the forms {sorted(WINO_FORMS)}')
+    return (int(winograd), *WINO_FORMS[int(winograd)])
+
+
+# Which F(4x4,3x3) kernel the policy hands out: WINO_F4 = csrc/conv2d_wino4.h (one 12-wave workgroup per CU, 8 x 64-pixel tiles, round 3), WINO_F4B = csrc/conv2d_wino4b.h
 # (two 8-wave workgroups per CU on the 16x16x4 MFMA, 8 x 32-pixel tiles, round 4).  Measured on the config-2 step (same box, profiles/r04_wino4_forms.txt): the
 # two-workgroup form is 1.5x faster on 32-pixel-wide images (no half-empty tiles, twice the workgroups) and 1-11 % slower everywhere else (twice the weight
 # stream from L2), so it serves images narrower than 64 pixels.  PG_WINO4B=0: never, PG_WINO4B=2: wherever F(4x4) runs (A/B runs).
 _WINO4B = os.environ.get('PG_WINO4B', '1')
-F4_FORM = 2 if _WINO4B == '0' else 3      # the form for narrow images (tests import this)
-# Round 6: 4 = the one-workgroup kernel with its transform-domain GEMM on the bf16 pipe (six products of exact three-term splits, fp32 accumulation; csrc/conv2d_wino4.h "X3"):
+F4_FORM = WINO_F4 if _WINO4B == '0' else WINO_F4B      # the form for narrow images (tests import this)
+# Round 6: WINO_F4X3 = the one-workgroup kernel with its transform-domain GEMM on the bf16 pipe (six products of exact three-term splits, fp32 accumulation; csrc/conv2d_wino4.h "X3"):
 # same results class (error against float64 at or below the fp32 form's, tools/wino4x3_probe.py), 1.03-1.26x faster per launch.  PG_WINO4_X3=0: the fp32-MFMA form (A/B runs).
-F4_WIDE = 2 if os.environ.get('PG_WINO4_X3', '1') == '0' else 4      # the form for images at least 64 pixels wide (tests import this)
+F4_WIDE = WINO_F4 if os.environ.get('PG_WINO4_X3', '1') == '0' else WINO_F4X3      # the form for images at least 64 pixels wide (tests import this)
 
 
 def f4_form(hw):
     if _WINO4B == '2':
-        return 3
+        return WINO_F4B
     return F4_FORM if int(hw[1]) < 64 else F4_WIDE
 
 
 def use_winograd(kh, kw, stride, cout, cin=None, x2=None, pad=None, hw=None, xf=False, ep=None):
-    """Launch policy for 3x3 stride-1 convolutions.  Returns 0 (direct implicit GEMM), 1 (Winograd F(2x2,3x3), csrc/conv2d_wino.h) or
-    2 (Winograd F(4x4,3x3), csrc/conv2d_wino4.h) -- truthy = some Winograd kernel, and the value is what `pack_weight(winograd=...)` /
+    """Launch policy for 3x3 stride-1 convolutions.  Returns 0 (direct implicit GEMM), WINO_F2 (Winograd F(2x2,3x3), csrc/conv2d_wino.h) or one of
+    the three F(4x4,3x3) forms (`f4_form`: WINO_F4B, csrc/conv2d_wino4b.h, for images narrower than 64 pixels, WINO_F4X3 -- or WINO_F4 under PG_WINO4_X3=0 --
+    of csrc/conv2d_wino4.h for the rest) -- truthy = some Winograd kernel, and the value is what `pack_weight(winograd=...)` /
     `conv2d_forward(winograd=...)` take.  F(4x4) needs the image size (`hw`): its 8 x 64-pixel tiles and 16-channel chunks pay on layers
-    with Cin >= 64, Cout a multiple of 64 and images of at least 32 x 32 (the two-workgroup form serves those narrower than 64 pixels: `f4_form`) whose width -- and output width -- is a multiple of 4; `xf` (an input pre-activation
+    with Cin >= 64, Cout a multiple of 64 and images of at least 32 x 32 whose width -- and output width -- is a multiple of 4; `xf` (an input pre-activation
     stage) stays on F(2x2).  PG_CONV_ALGO=direct|winograd|winograd2|winograd4 overrides (A/B measurements): 'winograd2' = never F(4x4),
     'winograd4' = F(4x4) wherever the kernel accepts the launch.  `ep` = the fused epilogue's keyword arguments when the caller has them: the
     F(4x4) tail evaluates the activation as max(v * gain, v * gain * slope), exact for gain > 0 and 0 <= alpha <= 1 only (the kernel declines
@@ -222,7 +223,7 @@ def use_winograd(kh, kw, stride, cout, cin=None, x2=None, pad=None, hw=None, xf=
     if mode == 'winograd4' and f4_possible:
         return f4_form(hw)
     if mode in ('winograd', 'winograd2', 'winograd4'):
-        return 1
+        return WINO_F2
     if not (int(cout) > 32 and (cin is None or int(cin) >= 16)):
         return 0
     if f4_possible and cin is not None and int(cin) >= 64 and int(cin) % 16 == 0 and int(cout) % 64 == 0 and int(hw[0]) >= 32 and int(hw[1]) >= 32:
@@ -230,7 +231,7 @@ def use_winograd(kh, kw, stride, cout, cin=None, x2=None, pad=None, hw=None, xf=
     # (16 x 16 images: the two-workgroup F(4x4) form beats F(2x2) there too -- 112 vs 177 us at N = 8, tools/wino_small_probe.py -- but F(4x4)'s ~15x larger
     # rounding error in one of the FIRST layers of the style branch is amplified by everything behind it: the generator-gradient parity test went from 9e-4
     # to 2.7e-3 worst signature mismatch (bar 2e-3).  65 us per step is not worth that margin: F(2x2) keeps the 8 x 8 and 16 x 16 layers.)
-    return 1
+    return WINO_F2
 
 
 def supported(kh, kw, stride):
@@ -246,25 +247,22 @@ def _f32c(t, name):
 
 
 def pack_weight(w, scale=1.0, flip=False, transpose_oi=False, winograd=False):
-    """OIHW (or IOHW when `transpose_oi`) float32 weights -> the kernel's [CinP][taps][CoutP] layout, or, with
-    `winograd` = 1 / True, the pre-transformed [16][CinP][CoutP64] layout of the F(2x2,3x3) kernel, with `winograd` = 2 the
-    36 * CinP * CoutP64 operand stream of the F(4x4,3x3) kernel (3x3 weights only)."""
+    """OIHW (or IOHW when `transpose_oi`) float32 weights -> the kernel's [CinP][taps][CoutP] layout, or, with `winograd` = a WINO_* form
+    (True = WINO_F2), the pre-transformed operand stream of that form's kernel (3x3 weights only; each form has its own order, and the
+    stream of one form serves no other: include/pasta_gan_ops.h)."""
     lib = _init().lib
     w = _f32c(w.detach(), 'weight')
     if transpose_oi:
         cin, cout, kh, kw = w.shape
     else:
         cout, cin, kh, kw = w.shape
-    if winograd:
+    form = _wino_form(winograd)[0]
+    if form:
         if (kh, kw) != (3, 3):
             raise nat.NativeOpError('conv2d_mfma: the Winograd layout is for 3x3 weights')
-        size, pack = ((lib.pg_conv2d_winograd4x3_packed_size, lib.pg_conv2d_winograd4x3_pack_weight) if int(winograd) == 4 else
-                      (lib.pg_conv2d_winograd4_packed_size, lib.pg_conv2d_winograd4b_pack_weight) if int(winograd) == 3 else
-                      (lib.pg_conv2d_winograd4_packed_size, lib.pg_conv2d_winograd4_pack_weight) if int(winograd) == 2 else
-                      (lib.pg_conv2d_winograd_packed_size, lib.pg_conv2d_winograd_pack_weight))
-        packed = torch.empty([size(cout, cin)], dtype=torch.float32, device=w.device)
+        packed = torch.empty([lib.pg_conv2d_winograd_packed_size(form, cout, cin)], dtype=torch.float32, device=w.device)
         with torch.cuda.device(w.device):
-            st = pack(nat.ptr(w), nat.ptr(packed), cout, cin, float(scale), int(bool(flip)), int(bool(transpose_oi)), nat.stream_of(w))
+            st = lib.pg_conv2d_winograd_pack_weight(form, nat.ptr(w), nat.ptr(packed), cout, cin, float(scale), int(bool(flip)), int(bool(transpose_oi)), nat.stream_of(w))
         nat.check(st, 'pg_conv2d_winograd_pack_weight')
         return packed
     packed = torch.empty([lib.pg_conv2d_packed_size(cout, cin, kh, kw)], dtype=torch.float32, device=w.device)
@@ -278,17 +276,18 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
                    in_scale=None, in_bias=None, in_act='linear', in_alpha=0.0, in_gain=1.0, in_clamp=None,
                    out_scale=None, noise=None, noise_gain=1.0, bias=None, act='linear', alpha=0.0, gain=1.0, clamp=None,
                    residual=None, spade=None, x2=None, winograd=False, stats_eps=None):
-    """One launch of the MFMA convolution (`winograd`: of its F(2x2,3x3) variant; `packed` must then come from
-    `pack_weight(..., winograd=True)`; 3x3 stride 1, no spade / x2).  `x` [N,Cin,H,W] float32 contiguous; `packed` from
+    """One launch of the MFMA convolution (`winograd` = a WINO_* form, True = WINO_F2: of that Winograd kernel; `packed` must then come from
+    `pack_weight(..., winograd=<the same form>)`; 3x3 stride 1, dense output, no x2).  `x` [N,Cin,H,W] float32 contiguous; `packed` from
     `pack_weight`.  Writes y[n, co, oy*step+off, ox*step+off] for oy < out_hw[0], ox < out_hw[1]
     (allocating a dense [N,Cout,OH,OW] `y` when none is given) and returns `y`.
     `spade=(x_norm, mean, rstd)` selects the SPADE combine epilogue: `packed` holds interleaved gamma/beta rows
     (`pack_spade_gamma_beta`), `cout` = 2*C, and the result is the [N, C, OH, OW] tensor
     (x_norm - mean) * rstd * (1 + gamma) + beta.
-    `stats_eps` (F(4x4) one-workgroup launches with the plain tail only: winograd=2, no in_scale / noise / residual / spade; anything else raises
+    `stats_eps` (F(4x4) one-workgroup launches with the plain tail only: winograd=WINO_F4 / WINO_F4X3, no in_scale / noise / residual / spade; anything else raises
     NativeNotCovered): also gather the instance-norm statistics of the OUTPUT where it is produced -- returns (y, (mean, rstd)) with
     rstd = 1 / sqrt(var + stats_eps), what `instance_norm_stats(y, stats_eps)` would compute in a second pass over y."""
     lib = _init().lib
+    form, label, has_stats_tail, _ = _wino_form(winograd)
     x = _f32c(x, 'x')
     n, cin, h, w = x.shape
     cin_split = 0
@@ -354,7 +353,7 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
         fz.x2, fz.cin_split = x2.data_ptr(), cin_split
     stats_part = None
     if stats_eps is not None:
-        if int(winograd) not in (2, 4) or spade is not None or in_scale is not None or noise is not None or residual is not None or x2 is not None or in_act != 'linear':
+        if not has_stats_tail or spade is not None or in_scale is not None or noise is not None or residual is not None or x2 is not None or in_act != 'linear':
             raise nat.NativeNotCovered('conv2d_mfma: output statistics are gathered by the F(4x4) kernel\'s plain tail only')
         stats_T = lib.pg_conv2d_winograd4_stats_tiles(int(oh), int(ow))
         stats_part = torch.empty([n * cout * stats_T * 2], dtype=torch.float32, device=x.device)
@@ -363,12 +362,11 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
         if _timeline is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        if winograd:
+        if form:
             if (kh, kw, int(stride)) != (3, 3, 1) or tuple(out_step) != (1, 1) or tuple(out_off) != (0, 0):
                 raise nat.NativeOpError('conv2d_mfma: winograd=True needs a 3x3 stride-1 dense-output launch')
-            fwd = {1: lib.pg_conv2d_winograd_forward, 2: lib.pg_conv2d_winograd4_forward, 3: lib.pg_conv2d_winograd4b_forward, 4: lib.pg_conv2d_winograd4x3_forward}[int(winograd)]
-            st = fwd(nat.ptr(x), nat.ptr(packed), nat.ptr(y), n, cin, h, w, cout, int(pad_y), int(pad_x),
-                     int(oh), int(ow), nat.i64arr(y.stride()), ctypes.byref(fz), nat.stream_of(x))
+            st = lib.pg_conv2d_winograd_forward(form, nat.ptr(x), nat.ptr(packed), nat.ptr(y), n, cin, h, w, cout, int(pad_y), int(pad_x),
+                                                int(oh), int(ow), nat.i64arr(y.stride()), ctypes.byref(fz), nat.stream_of(x))
         else:
             ksplit = 1
             if spade is None and x2 is None and os.environ.get('PG_CONV_SPLITK', '1') != '0':
@@ -384,7 +382,7 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
                                            ctypes.byref(fz), nat.stream_of(x))
         if _timeline is not None:
             ev1.record()
-            _timeline.append(((kh, kw, int(stride), ('winograd4x3' if int(winograd) == 4 else 'winograd4' if int(winograd) >= 2 else 'winograd') if winograd else 'direct', f'N{n} {cin}->{cout} {h}x{w}' + (' spade' if spade is not None else '') + (' xf' if in_act != 'linear' else '') + (' mod' if in_scale is not None else '') + (' res' if residual is not None else '')), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1,
+            _timeline.append(((kh, kw, int(stride), label, f'N{n} {cin}->{cout} {h}x{w}' + (' spade' if spade is not None else '') + (' xf' if in_act != 'linear' else '') + (' mod' if in_scale is not None else '') + (' res' if residual is not None else '')), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1,
                               4 * (x.numel() + (x2.numel() if x2 is not None else 0) + n * ychan * oh * ow)))
     nat.check(st, 'pg_conv2d_forward')
     if stats_part is not None:
@@ -405,9 +403,9 @@ def pack_spade_gamma_beta(w_gamma, w_beta, scale_gamma=1.0, scale_beta=1.0, wino
     c = int(w_gamma.shape[0])
     grp = 32
     assert w_gamma.shape == w_beta.shape and c % 32 == 0
-    if int(winograd) == 3:      # the two-workgroup F(4x4) kernel finishes rows (2c, 2c + 1) in one lane: gamma / beta of a channel as ADJACENT rows
+    if _wino_form(winograd)[3]:      # the two-workgroup F(4x4) kernel finishes rows (2c, 2c + 1) in one lane: gamma / beta of a channel as ADJACENT rows
         gw, bw = w_gamma.detach() * scale_gamma, w_beta.detach() * scale_beta
-        return pack_weight(torch.stack([gw, bw], dim=1).reshape(2 * c, *w_gamma.shape[1:]).contiguous(), winograd=3)
+        return pack_weight(torch.stack([gw, bw], dim=1).reshape(2 * c, *w_gamma.shape[1:]).contiguous(), winograd=winograd)
     g = (w_gamma.detach() * scale_gamma).reshape(c // grp, grp, *w_gamma.shape[1:])
     b = (w_beta.detach() * scale_beta).reshape(c // grp, grp, *w_beta.shape[1:])
     return pack_weight(torch.cat([g, b], dim=1).reshape(2 * c, *w_gamma.shape[1:]).contiguous(), winograd=winograd)

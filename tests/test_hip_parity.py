@@ -656,6 +656,96 @@ def test_conv2d_winograd4_policy_and_declines():
         conv2d_mfma.conv2d_forward(x, conv2d_mfma.pack_weight(wt, winograd=3), 64, 3, 3, pad=(1, 1), winograd=3)
     with pytest.raises(NativeNotCovered):
         conv2d_mfma.conv2d_forward(x, conv2d_mfma.pack_weight(wt, winograd=4), 64, 3, 3, pad=(1, 1), winograd=4)
+    # a form outside PG_WINO_*: the C entry points return PG_ERR_INVALID_ARG before anything is launched (valid pointers, an accepted geometry)
+    import ctypes
+    from torch_utils.ops import _native as nat
+    lib = conv2d_mfma._init().lib
+    xs = xa.to(DEV)
+    pk = torch.zeros([lib.pg_conv2d_winograd_packed_size(conv2d_mfma.WINO_F4X3, 64, 64)], device=DEV)
+    ys = torch.zeros([1, 64, 32, 64], device=DEV)
+    for bad in (0, 5):
+        with torch.cuda.device(xs.device):
+            assert lib.pg_conv2d_winograd_pack_weight(bad, nat.ptr(wa.to(DEV)), nat.ptr(pk), 64, 64, 1.0, 0, 0, nat.stream_of(xs)) == -1
+            assert lib.pg_conv2d_winograd_forward(bad, nat.ptr(xs), nat.ptr(pk), nat.ptr(ys), 1, 64, 32, 64, 64, 1, 1, 32, 64,
+                                                  nat.i64arr(ys.stride()), ctypes.byref(conv2d_mfma.Fusion()), nat.stream_of(xs)) == -1
+    torch.cuda.synchronize()
+    assert not pk.any() and not ys.any()
+
+
+def _winograd_exact_u(form, k, mult, scale, flip, transpose_oi):
+    """U = G g G^T [co][ci][a][b] of the weight `mult * k` (`k` integers) as `pack_weight(..., scale, flip, transpose_oi)` reads it, exactly: G = GI / den with
+    an integer GI, so U = (GI k GI^T) * (mult * scale / den^2) is integer arithmetic in float64."""
+    g = k.double()
+    if transpose_oi:                                  # the tensor is IOHW
+        g = g.transpose(0, 1)
+    if flip:
+        g = g.flip(2, 3)
+    if form == 1:
+        GI, den = torch.tensor([[2, 0, 0], [1, 1, 1], [1, -1, 1], [0, 0, 2]], dtype=torch.float64), 2
+    else:
+        GI, den = torch.tensor([[6, 0, 0], [-4, -4, -4], [-4, 4, -4], [1, 2, 4], [1, -2, 4], [0, 0, 24]], dtype=torch.float64), 24
+    return torch.einsum('ak,oikl,bl->oiab', GI, g, GI) * (mult * scale / den ** 2)
+
+
+def _winograd_host_stream(form, U):
+    """The operand stream of form `form` for the exact transformed weights U, from the layout comments of include/pasta_gan_ops.h / csrc/conv2d.hip: float32
+    words (forms 1-3) or 16-bit words (form 4); rows and channels beyond Cout / Cin are zero."""
+    cout, cin = U.shape[:2]
+    coutp, cinp = -(-cout // 64) * 64, -(-cin // 16) * 16
+    Up = torch.zeros([coutp, cinp, *U.shape[2:]], dtype=torch.float64)
+    Up[:cout, :cin] = U
+    if form == 1:        # [a][co / 32][ci / 2][ci & 1][co & 31][b]
+        return Up.view(coutp // 32, 32, cinp // 2, 2, 4, 4).permute(4, 0, 2, 3, 1, 5).reshape(-1).float()
+    if form == 2:        # [m-block 64][mt][a][chunk][jg][quad][jj][lane = (h, co & 31)][s]: b = 3 jg + jj, channel = 16 chunk + 2 (4 quad + s) + h
+        return Up.view(coutp // 64, 2, 32, cinp // 16, 2, 4, 2, 6, 2, 3).permute(0, 1, 7, 3, 8, 4, 9, 6, 2, 5).reshape(-1).float()
+    if form == 3:        # [m-block 64][cb 4][ah 2][chunk][e = 6 a' + b][lane = (kq, m 16)][j 4]: a = 3 ah + a', cout = 64 mb + 16 cb + m, channel = 16 chunk + 4 j + kq
+        return Up.view(coutp // 64, 4, 16, cinp // 16, 4, 4, 2, 3, 6).permute(0, 1, 6, 3, 7, 8, 5, 2, 4).reshape(-1).float()
+    # form 4: [m-block 64][mt][a][chunk][b 6][plane 3][lane = (h, co & 31)][j 8] 16-bit words, channel = 16 chunk + 2 j + h; planes = the truncation split of float32(U)
+    u = Up.float()
+    p0 = (u.view(torch.int32) & -65536).view(torch.float32)
+    r = u - p0
+    p1 = (r.view(torch.int32) & -65536).view(torch.float32)
+    p2 = ((r - p1).view(torch.int32) & -65536).view(torch.float32)
+    assert torch.equal(p0.double() + p1.double() + p2.double(), Up)                       # three bf16 planes hold it exactly
+    planes = (torch.stack([p0, p1, p2], dim=-1).view(torch.int32) >> 16).to(torch.int16)  # [co][ci][a][b][plane]
+    return planes.view(coutp // 64, 2, 32, cinp // 16, 8, 2, 6, 6, 3).permute(0, 1, 6, 3, 7, 8, 5, 2, 4).reshape(-1)
+
+
+@pytest.mark.parametrize('form', [1, 2, 3, 4])
+def test_winograd_pack_streams_equal_the_documented_layout(form):
+    """The packed operand stream of every Winograd form, word for word against a host build of the documented layout (the convolution tests reach the streams
+    only through their tolerances).  Exact by choice of input: weights of 576 x integers in [-8, 8] (F(2x2): 4 x) make every transformed weight an integer
+    below 2^24; the kernel's float64 value is that integer up to ~2^-32 (G's sixths are not exact), so its ONE rounding to float32 gives the integer whatever
+    the contraction of the arithmetic, and the three-plane bf16 split of it is exact.  Two things that premise needs, both asserted here:
+      * the transformed weights are integer-valued (under scale = 0.5 the integers are the even ones of the range for that reason);
+      * none of them is 0 inside Cout x Cin: where the exact value is 0 the float64 residue (~1e-14) is what float32 keeps, and no host build can predict
+        it -- a 3x3 kernel whose transform has a zero is drawn again (about half of them).  The padded rows and channels are true zeros (of either sign: the
+        16-bit words of form 4 are compared as the bf16 values they are).
+    Shapes: one block; both paddings; several m-blocks and chunks.  Each plain, as a flipped IOHW weight, and scaled."""
+    from torch_utils.ops import conv2d_mfma
+    mult = 4.0 if form == 1 else 576.0
+    gen = torch.Generator().manual_seed(1000 + form)
+    for cout, cin in ((64, 16), (70, 20), (128, 48)):
+        for scale, flip_t in ((1.0, False), (1.0, True), (0.5, False)):
+            step = 1 if scale == 1.0 else 2
+
+            def draw(shape):
+                return torch.randint(-8 // step, 8 // step + 1, shape, generator=gen) * step
+
+            k = draw([cin, cout, 3, 3] if flip_t else [cout, cin, 3, 3])
+            for _ in range(64):
+                U = _winograd_exact_u(form, k, mult, scale, flip_t, flip_t)
+                redo = (U == 0).flatten(2).any(2)                   # [co][ci]
+                if not redo.any():
+                    break
+                redo = redo.t() if flip_t else redo
+                k[redo] = draw([int(redo.sum()), 3, 3])
+            assert torch.equal(U, U.round()) and bool((U != 0).all()) and float(U.abs().max()) < 2 ** 24, 'the premise of the exact comparison'
+            want = _winograd_host_stream(form, U)
+            got = conv2d_mfma.pack_weight((k.float() * mult).to(DEV), scale=scale, flip=flip_t, transpose_oi=flip_t, winograd=form).cpu()
+            if form == 4:
+                got, want = got.view(torch.bfloat16), want.view(torch.bfloat16)
+            assert got.shape == want.shape and torch.equal(got, want), (form, cout, cin, scale, flip_t)
 
 
 @pytest.mark.parametrize('n,cin,cout,h,w', [(8, 128, 128, 256, 256), (8, 64, 64, 512, 512), (2, 512, 512, 64, 64), (2, 80, 70, 24, 72)])

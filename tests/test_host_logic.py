@@ -44,7 +44,12 @@ def test_c_abi_libraries_export_every_declared_symbol():
     assert conv.pg_conv2d_packed_size(3, 64, 1, 1) == 64 * 1 * 32
     assert conv.pg_conv2d_packed_size(0, 64, 1, 1) == 0
     conv.pg_conv2d_winograd_packed_size.restype = ctypes.c_int64
-    assert conv.pg_conv2d_winograd_packed_size(70, 20) == 16 * 32 * 128            # [16 positions][CinP = 32][CoutP64 = 128]
+    PG_WINO_F2, PG_WINO_F4, PG_WINO_F4B, PG_WINO_F4X3 = 1, 2, 3, 4
+    assert conv.pg_conv2d_winograd_packed_size(PG_WINO_F2, 70, 20) == 16 * 32 * 128            # [16 positions][CinP = 32][CoutP64 = 128]
+    assert conv.pg_conv2d_winograd_packed_size(PG_WINO_F4, 70, 20) == 36 * 32 * 128            # [36 positions] in the one-workgroup form's order ...
+    assert conv.pg_conv2d_winograd_packed_size(PG_WINO_F4B, 70, 20) == 36 * 32 * 128           # ... and in the two-workgroup form's
+    assert conv.pg_conv2d_winograd_packed_size(PG_WINO_F4X3, 70, 20) == 54 * 32 * 128          # 36 positions x three 16-bit planes, in float32 units
+    assert conv.pg_conv2d_winograd_packed_size(0, 70, 20) == 0 and conv.pg_conv2d_winograd_packed_size(5, 70, 20) == 0      # no such form
     # host-only: the split-K planner (no GPU touched)
     plan = conv.pg_conv2d_splitk_plan
     plan.restype = ctypes.c_int

@@ -63,8 +63,9 @@ if what in ('time', 'all'):
     for (N, H, cin, cout) in [(8, 256, 128, 128), (8, 256, 128, 256), (8, 512, 64, 64), (8, 512, 64, 128), (8, 128, 256, 256), (8, 64, 512, 512), (8, 32, 512, 512), (4, 256, 128, 128), (4, 512, 64, 64)]:
         x = torch.randn(N, cin, H, H, device=dev)
         w = torch.randn(cout, cin, 3, 3, device=dev) / (3 * cin ** 0.5)
-        pk = {a: conv2d_mfma.pack_weight(w, winograd=a) for a in (2, 4)}
-        ms = {a: timeit(lambda a=a: conv2d_mfma.conv2d_forward(x, pk[a], cout, 3, 3, pad=(1, 1), winograd=a)) for a in (2, 4)}
+        forms = (conv2d_mfma.WINO_F4, conv2d_mfma.WINO_F4X3)      # 2, 4: the keys of `ms` below
+        pk = {a: conv2d_mfma.pack_weight(w, winograd=a) for a in forms}
+        ms = {a: timeit(lambda a=a: conv2d_mfma.conv2d_forward(x, pk[a], cout, 3, 3, pad=(1, 1), winograd=a)) for a in forms}
         fl = 2.0 * N * cout * H * H * cin * 9 / 4
         print(f'N{N} H{H} cin{cin:4d} cout{cout:4d}: fp32 form {ms[2]*1e3:8.1f} us = {fl/ms[2]/1e9:6.1f} TF ({fl/ms[2]/1e9/157.3:.3f}) | X3 {ms[4]*1e3:8.1f} us = {fl/ms[4]/1e9:6.1f} TF fp32-equivalent '
               f'({fl/ms[4]/1e9/157.3:.3f} of the fp32 peak; executed 6x: {6*fl/ms[4]/1e9/2500:.3f} of the bf16 peak)  x{ms[2]/ms[4]:.2f}', flush=True)
