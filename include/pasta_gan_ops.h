@@ -359,6 +359,18 @@ int pg_instance_norm_stats(const float* x, float* mean, float* rstd, int NC, int
 int pg_spade_norm(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                   float* y, int NC, int64_t HW, void* stream);
 
+/* The two passes above for the 16-bit (PG_BF16 | PG_F16) CHANNELS-LAST route (csrc/spade16.hip): x, y [N, H, W, C], C % 16 == 0, 16-byte aligned, HW = H * W.
+ *   pg_instance_norm_stats_cl16: mean / rstd [N, C] float32 (biased variance), float32 accumulation of shifted data in two levels -- per pixel chunk, then
+ *     over the chunks in chunk order; no atomics, bit-identical from run to run.  `workspace`: 2 * N * PG_STATS16_MAX_CHUNKS * C floats.  C <= 2048, N <= 65535.
+ *   pg_spade_combine_cl16: y = clamp(act(((x - mean) * rstd) * (1 + gamma) + beta) * gain), gamma_beta [N, H, W, 2C] with gamma in the first C channels of a
+ *     pixel (the output of the stacked gamma || beta convolution); act = PG_ACT_LINEAR (or 0) | PG_ACT_RELU | PG_ACT_LRELU (slope alpha); clamp < 0 disables
+ *     it; rounded to the 16-bit type once, on the store.  N * HW * C / 8 < 2^31 (PG_ERR_TOO_LARGE otherwise).
+ * PG_ERR_UNSUPPORTED: channel count, alignment or activation not covered. */
+#define PG_STATS16_MAX_CHUNKS 256
+int pg_instance_norm_stats_cl16(const void* x, float* mean, float* rstd, float* workspace, int dtype, int N, int64_t HW, int C, float eps, void* stream);
+int pg_spade_combine_cl16(const void* x, const float* mean, const float* rstd, const void* gamma_beta, void* y, int dtype, int N, int64_t HW, int C,
+                          int act, float alpha, float gain, float clamp, void* stream);
+
 /* The same combine on the TRAINING route, with its gradient (autograd of networks.py:1715-1723: instance norm, then x_hat (1 + gamma) + beta).
  * x, y, dy, dx: [N, C, HW] contiguous.  gamma / beta (and dgamma / dbeta) may be planes of a larger tensor -- the two 3x3 convolutions that
  * produce them run as one launch over the stacked weights, output [N, 2C, HW]: plane (n, c) starts at base + n * sample_stride + c * HW.

@@ -63,6 +63,10 @@ def _init():
         lib.pg_conv2d16_wgrad_plan.argtypes = [i] * 8
         lib.pg_conv2d16_wgrad.restype = i
         lib.pg_conv2d16_wgrad.argtypes = [vp, vp, vp, vp, i] + [i] * 13 + [vp]
+        lib.pg_instance_norm_stats_cl16.restype = i
+        lib.pg_instance_norm_stats_cl16.argtypes = [vp, vp, vp, vp, i, i, i64, i, f, vp]
+        lib.pg_spade_combine_cl16.restype = i
+        lib.pg_spade_combine_cl16.argtypes = [vp, vp, vp, vp, vp, i, i, i64, i, i, f, f, f, vp]
         _lib = lib
     return _lib
 
@@ -432,4 +436,55 @@ def conv1x1_small(x, w, styles=None, bias=None, skip=None, clamp=None, skip_up2=
         st = lib.pg_conv1x1_small16(nat.ptr(x), nat.ptr(w), nat.ptr(styles), nat.ptr(bias), nat.ptr(skip), nat.ptr(y), nat.PG_DTYPE[x.dtype],
                                     n, cin, h * wd, cout, -1.0 if clamp is None else float(clamp), wd if (skip_up2 and skip is not None) else 0, nat.stream_of(x))
     nat.check(st, 'pg_conv1x1_small16')
+    return y
+
+
+STATS16_MAX_CHUNKS = 256        # PG_STATS16_MAX_CHUNKS of include/pasta_gan_ops.h
+
+
+def _cl16(t, name):
+    if t.dtype not in DTYPES or not t.is_cuda or t.ndim != 4:
+        raise nat.NativeOpError(f'conv2d_mfma16: {name} must be a 4-D bf16 / fp16 GPU tensor')
+    if t.shape[1] % 16 != 0:
+        raise nat.NativeOpError(f'conv2d_mfma16: {name} must have a multiple of 16 channels')
+    return to_channels_last(t)
+
+
+def instance_norm_stats16(x, eps=1e-5):
+    """Per-(n, c) mean and 1 / sqrt(var + eps) (biased variance) of a 16-bit [N, C, H, W] tensor in channels-last storage (converted if it is not),
+    C % 16 == 0: float32 [N * C] each, what `conv2d_mfma.instance_norm_stats` returns for the float32 tensor.  float32 accumulation in a fixed order
+    (csrc/spade16.hip): repeats are bit-identical."""
+    lib = _init()
+    x = _cl16(x, 'x')
+    n, c, h, w = x.shape
+    mean = torch.empty([n * c], dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    ws = torch.empty([2 * n * STATS16_MAX_CHUNKS * c], dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        st = lib.pg_instance_norm_stats_cl16(nat.ptr(x), nat.ptr(mean), nat.ptr(rstd), nat.ptr(ws), nat.PG_DTYPE[x.dtype], n, h * w, c, float(eps), nat.stream_of(x))
+    nat.check(st, 'pg_instance_norm_stats_cl16')
+    return mean, rstd
+
+
+def spade_combine16(x, mean, rstd, gamma_beta, act='linear', alpha=0.0, gain=1.0, clamp=None, y=None):
+    """clamp(act(((x - mean) * rstd) * (1 + gamma) + beta) * gain) in one streaming pass (networks.py:1715-1723 and the consumer's pre-activation,
+    :1627-1633): x 16-bit [N, C, H, W] channels-last, mean / rstd float32 [N * C] (`instance_norm_stats16`), gamma_beta [N, 2C, H, W] of x's dtype,
+    channels-last, gamma = its first C channels.  Returns a channels-last tensor of x's dtype (`y`, when given, is written instead)."""
+    lib = _init()
+    x = _cl16(x, 'x')
+    n, c, h, w = x.shape
+    if gamma_beta.dtype != x.dtype or tuple(gamma_beta.shape) != (n, 2 * c, h, w):
+        raise nat.NativeOpError('conv2d_mfma16: gamma_beta must be [N, 2C, H, W] of x\'s dtype')
+    gamma_beta = _cl16(gamma_beta, 'gamma_beta')
+    mean, rstd = _f32(mean, 'mean', n * c), _f32(rstd, 'rstd', n * c)
+    if act not in FUSED_ACTS:
+        raise nat.NativeOpError(f'conv2d_mfma16: spade_combine16 applies {FUSED_ACTS}, not {act!r}')
+    if y is None:
+        y = torch.empty_like(x, memory_format=torch.channels_last)
+    elif y.dtype != x.dtype or y.shape != x.shape or y.device != x.device or not y.is_contiguous(memory_format=torch.channels_last):
+        raise nat.NativeOpError('conv2d_mfma16: y must match x in dtype, shape and channels-last storage')
+    with torch.cuda.device(x.device):
+        st = lib.pg_spade_combine_cl16(nat.ptr(x), nat.ptr(mean), nat.ptr(rstd), nat.ptr(gamma_beta), nat.ptr(y), nat.PG_DTYPE[x.dtype], n, h * w, c,
+                                       ACT_INDEX[act], float(alpha or 0.0), float(gain), -1.0 if clamp is None else float(clamp), nat.stream_of(x))
+    nat.check(st, 'pg_spade_combine_cl16')
     return y

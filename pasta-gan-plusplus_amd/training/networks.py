@@ -811,6 +811,12 @@ class _ConvBase(nn.Module):
         k = int(self.weight.shape[2])
         return self.up == 1 and conv2d_mfma.supported(k, k, self.down) and self.activation in conv2d_mfma.FUSED_ACTS
 
+    def _fast16_geometry(self, x, *others):
+        """16-bit inference: a stride-1 layer the 16-bit MFMA convolution runs in one launch on these tensors."""
+        k = int(self.weight.shape[2])
+        return (_fast16_ok(x, self.weight, self.bias, *others) and self.up == 1 and self.down == 1 and conv2d_mfma16.supported(k, k, 1)
+                and self.activation in conv2d_mfma16.FUSED_ACTS)
+
 
 class Conv2dLayer(_ConvBase):
     """conv2d_resample -> bias_act (networks.py:170-179); `residual` (private) is added to the result."""
@@ -830,6 +836,12 @@ class Conv2dLayer(_ConvBase):
             pass
         if x2 is not None:
             x, x2 = torch.cat([x, x2], dim=1), None
+            if self._fast16_geometry(x, residual):
+                # 16-bit inference (the try-on generator's half mode, merge_conv): the two channels-last inputs concatenated, then ONE launch of the 16-bit
+                # MFMA convolution with bias / activation / gain / clamp (/ residual) in its epilogue
+                packed = self._cache.get(('plain16', x.dtype), [self.weight], lambda: conv2d_mfma16.pack_weight(self.weight, x.dtype, scale=self.weight_gain)[0])
+                return conv2d_mfma16.conv2d_forward(x, packed, cout, k, k, pad=(self.padding, self.padding), bias=self.bias, act=self.activation,
+                                                    alpha=bias_act.activation_funcs[self.activation].def_alpha, gain=act_gain, clamp=act_clamp, residual=residual)
         w = _gained_weight(self)
         b = self.bias.to(x.dtype) if self.bias is not None else None
         # conv2d_resample -> bias_act (networks.py:176-178); on the GPU the bias_act rides in the convolution's epilogue where that is the route's last step
@@ -918,6 +930,11 @@ class Spade_Conv2dLayer(_ConvBase):
         act_gain = self.act_gain * gain
         act_clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
         cout, _, k, _ = self.weight.shape
+        if no_act and self._fast16_geometry(x, residual):
+            # 16-bit inference (half mode): one launch, ReLU / residual in the epilogue; the statistics of the output by the channels-last pass over it
+            packed = self._cache.get(('plain16', x.dtype), [self.weight], lambda: conv2d_mfma16.pack_weight(self.weight, x.dtype, scale=self.weight_gain)[0])
+            y = conv2d_mfma16.conv2d_forward(x, packed, cout, k, k, pad=(self.padding, self.padding), act=post_act, residual=residual)
+            return y if stats_eps is None else (y, conv2d_mfma16.instance_norm_stats16(y, eps=stats_eps))
         # a pre-activation bias cannot ride in the conv prologue (zero padding); none of the generator's SPADE convs has one
         if _fast_ok(x, self.weight, self.bias, residual) and self._fast_geometry() and self.down == 1 and (no_act or self.bias is None):
             pro = {} if no_act else dict(in_act=self.activation, in_gain=act_gain, in_clamp=act_clamp,
@@ -993,6 +1010,8 @@ class Spade_Norm_Block(nn.Module):
         """`post` (private): dict(act, alpha, gain, clamp) -- the pre-activation of the one Spade_Conv2dLayer consuming the
         result (networks.py:1627-1633), applied here so that the consumer runs without a prologue.  `stats` (private):
         (mean, rstd) of x when the caller already has them (two norm blocks of a res-block normalise the same tensor)."""
+        if _fast16_ok(x, denorm_feats, self.conv_mlp.weight, self.conv_gamma.weight, self.conv_beta.weight):
+            return self._forward16(x, denorm_feats, post or {}, stats)
         if _fast_ok(x, denorm_feats, self.conv_mlp.weight, self.conv_gamma.weight, self.conv_beta.weight):
             post = post or {}
             mean, rstd = stats if stats is not None else conv2d_mfma.instance_norm_stats(x, eps=self.param_free_norm.eps)
@@ -1030,6 +1049,23 @@ class Spade_Norm_Block(nn.Module):
         return normalized * (1 + gamma) + beta
 
 
+    def _forward16(self, x, denorm_feats, post, stats):
+        """16-bit inference (half mode), x channels-last bf16 / fp16: conv_mlp + ReLU in one launch (the one-channel parsing map keeps the float32 stencil, its
+        output is cast), gamma || beta as ONE convolution over the stacked weights, then the streaming combine with the consumer's pre-activation."""
+        mean, rstd = stats if stats is not None else conv2d_mfma16.instance_norm_stats16(x, eps=self.param_free_norm.eps)
+        m, g, b = self.conv_mlp, self.conv_gamma, self.conv_beta
+        if (denorm_feats.dtype == torch.float32 and conv2d_mfma.conv3x3_cin1_ok(denorm_feats, m.weight, m.padding) and m.up == 1 and m.down == 1
+                and os.environ.get('PG_CIN1_STENCIL', '1') != '0'):
+            actv = conv2d_mfma.conv3x3_cin1(denorm_feats, m.weight, scale=m.weight_gain, act='relu').to(dtype=x.dtype, memory_format=torch.channels_last)
+        else:
+            actv = m(denorm_feats.to(dtype=x.dtype, memory_format=torch.channels_last), no_act=True, post_act='relu')
+        c = int(g.weight.shape[0])
+        packed = self._cache.get(('gamma_beta16', x.dtype), [g.weight, b.weight],
+                                 lambda: conv2d_mfma16.pack_weight(torch.cat([g.weight.detach() * g.weight_gain, b.weight.detach() * b.weight_gain]), x.dtype)[0])
+        gb = conv2d_mfma16.conv2d_forward(actv, packed, 2 * c, 3, 3, pad=(g.padding, g.padding))
+        return conv2d_mfma16.spade_combine16(x, mean, rstd, gb, **post)
+
+
 class Spade_ResBlockV4_512(nn.Module):
     def __init__(self, in_channels, out_channels, spade_channels, kernel_size=3, bias=True, activation='linear', up=1, down=1,
                  resample_filter=[1, 3, 3, 1], conv_clamp=None, channels_last=False, trainable=True, resolution=256):
@@ -1045,7 +1081,7 @@ class Spade_ResBlockV4_512(nn.Module):
         self.spade1 = Spade_Norm_Block(spade_channels, out_channels)
 
     def forward(self, x, denorm_feat):
-        if _fast_ok(x, denorm_feat, self.conv.weight, self.conv0.weight) and all(l.bias is None and l.activation in conv2d_mfma.FUSED_ACTS for l in (self.skip, self.conv0, self.conv1)):
+        if (_fast_ok(x, denorm_feat, self.conv.weight, self.conv0.weight) or _fast16_ok(x, denorm_feat, self.conv.weight, self.conv0.weight)) and all(l.bias is None and l.activation in conv2d_mfma.FUSED_ACTS for l in (self.skip, self.conv0, self.conv1)):
             # inference route: each SPADE output feeds exactly one convolution, so that convolution's pre-activation is applied
             # where the SPADE output is produced and the convolutions run without a prologue; the statistics the norm blocks need come out of
             # the tail of the convolution that produces their input (round 4: no second pass over x / dx)
@@ -1216,6 +1252,7 @@ class _SynthesisBlockBase(nn.Module):
         self.in_channels, self.w_dim, self.resolution, self.img_channels = in_channels, w_dim, resolution, img_channels
         self.is_last, self.architecture, self.use_fp16 = is_last, architecture, use_fp16
         self.channels_last = (use_fp16 and fp16_channels_last)
+        self.half_dtype = None          # SynthesisNetworkFull_v18.set_half: the 16-bit type of this block's inference forward (channels-last), None = float32
         self.register_buffer('resample_filter', upfirdn2d.setup_filter(resample_filter))
         first = in_channels == 0
         layer = dict(w_dim=w_dim, resolution=resolution, conv_clamp=conv_clamp, channels_last=self.channels_last, **layer_kwargs)
@@ -1290,9 +1327,9 @@ class _SynthesisBlockBase(nn.Module):
         """`styles` (private): the block's affine outputs in `affine_layers()` order when the network computed them for all layers at once.
         `_feat_unused` (private): the caller does not read the returned feature map (the network's last style block); it may come back as None."""
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
-        half = self.use_fp16 and not force_fp32
-        fmt = dict(dtype=torch.float16 if half else torch.float32,
-                   memory_format=torch.channels_last if (self.channels_last and not force_fp32) else torch.contiguous_format)
+        half = (self.use_fp16 or self.half_dtype is not None) and not force_fp32
+        fmt = dict(dtype=(self.half_dtype or torch.float16) if half else torch.float32,
+                   memory_format=torch.channels_last if ((self.channels_last or self.half_dtype is not None) and not force_fp32) else torch.contiguous_format)
         if fused_modconv is None:      # the reference's rule (networks.py:2152-2154); both forms are one launch here
             fused_modconv = (not self.training) and (not half or int(ws.shape[0]) == 1)
         style = lambda i: ws[:, i]
@@ -1391,7 +1428,8 @@ def _batched_affine(owner, entries, ws, num_ws, w_dim):
 
 class SynthesisNetworkFull_v18(nn.Module):
     """The 512^2 try-on generator body (reference networks.py:2198-2327): style branch b8..b512, garment-feature encoder,
-    two SPADE blocks at 256^2 and the texture block at 512^2.  float32 throughout, like the reference (:2223, :2294)."""
+    two SPADE blocks at 256^2 and the texture block at 512^2.  float32 throughout, like the reference (:2223, :2294), unless `set_half` switches the
+    inference forward of the high-resolution blocks to bf16 / fp16."""
 
     def __init__(self, w_dim, img_resolution, img_channels, channel_base=32768, channel_max=512, num_fp16_res=0, **block_kwargs):
         assert img_resolution >= 8 and img_resolution & (img_resolution - 1) == 0
@@ -1417,6 +1455,30 @@ class SynthesisNetworkFull_v18(nn.Module):
             ResBlock(ngf, ngf, kernel_size=4, activation='relu'),                 # 512
             ResBlock(ngf, ngf * 2, kernel_size=4, activation='relu', down=2),     # 256
         )
+        self.half_dtype, self.half_from_res = None, 64
+
+    def set_half(self, dtype, from_res=64):
+        """Opt-in 16-bit inference: run the blocks at resolution >= `from_res` -- the style blocks, the two SPADE blocks at the second-highest resolution and
+        the texture block with its SPADE block -- in `dtype` (torch.bfloat16 | torch.float16), channels-last, on the 16-bit kernels; None restores the float32
+        route exactly.  A plain attribute switch (no parameter is touched: call it after loading a checkpoint); `num_fp16_res` stays ignored.  Mapping, both
+        encoders, the garment-feature encoder and assembly, the blocks below `from_res`, the running skip image, `pred_parsing` and both returned images stay
+        float32.  The 16-bit route is inference on the GPU only: with autograd enabled, in training mode or on CPU tensors the blocks run their float32 code
+        (on a CPU network `set_half` changes nothing in the arithmetic).  Returns self."""
+        if dtype is not None and dtype not in conv2d_mfma16.DTYPES:
+            raise ValueError(f'set_half: dtype must be None, torch.bfloat16 or torch.float16, not {dtype!r}')
+        if dtype is not None:
+            narrow = [res for res in self.block_resolutions if res >= int(from_res) and any(int(c) % 16 for c in (getattr(self, f'b{res}').in_channels, getattr(self, f'b{res}').conv1.weight.shape[0]))]
+            if narrow:
+                raise ValueError(f'set_half: the 16-bit kernels need channel counts that are multiples of 16; the blocks at {narrow} have narrower layers')
+        self.half_dtype, self.half_from_res = dtype, int(from_res)
+        for res in self.block_resolutions:
+            getattr(self, f'b{res}').half_dtype = dtype if res >= int(from_res) else None
+        self.texture_b512.half_dtype = dtype if self.block_resolutions[-1] >= int(from_res) else None
+        return self
+
+    def _half_on(self, block, ws):
+        """This call runs `block` in its 16-bit type: inference (no autograd, eval mode) on GPU tensors."""
+        return block.half_dtype is not None and ws.is_cuda and not torch.is_grad_enabled() and not self.training
 
     def get_spade_feat(self, mask_512, denorm_mask, denorm_input):
         """Garment features of one branch (reference :2253-2276): encode the warped garment inside the predicted region,
@@ -1480,8 +1542,9 @@ class SynthesisNetworkFull_v18(nn.Module):
         kept = {}
         for res, w in zip(self.block_resolutions, styles):
             # (the last style block's feature map is read by nobody -- the texture branch starts from kept[256] --: the block may fold its merge_conv into its heads)
-            x, img, pred_parsing = getattr(self, f'b{res}')(x, img, w, pose_feat, cat_feat, force_fp32=True, styles=pre[res] if pre is not None else None,
-                                                            _feat_unused=(res == self.block_resolutions[-1]), **block_kwargs)
+            block = getattr(self, f'b{res}')
+            x, img, pred_parsing = block(x, img, w, pose_feat, cat_feat, force_fp32=not self._half_on(block, ws), styles=pre[res] if pre is not None else None,
+                                         _feat_unused=(res == self.block_resolutions[-1]), **block_kwargs)
             kept[res] = (x, img)       # neither is modified in place afterwards: no clone needed
         x_256, img_256 = kept[self.block_resolutions[-2]]
 
@@ -1501,8 +1564,10 @@ class SynthesisNetworkFull_v18(nn.Module):
             spade_feat = (self.get_spade_feat(upper_mask.detach(), denorm_upper_mask, denorm_upper_input) * (_half_nearest(upper_mask) > 0.9)
                           + self.get_spade_feat(lower_mask.detach(), denorm_lower_mask, denorm_lower_input) * (_half_nearest(lower_mask) > 0.9))
 
+        if x_256.dtype != torch.float32:       # half mode: the 128-channel garment features are cast once for the six norm blocks that read them
+            spade_feat = spade_feat.to(dtype=x_256.dtype, memory_format=torch.channels_last)
         x_spade = self.spade_b256_2(self.spade_b256_1(x_256, spade_feat), spade_feat)
-        _, finetune_img, _ = self.texture_b512(x_spade, img_256, styles[-1], pose_feat, cat_feat, parsing_index, force_fp32=True,
+        _, finetune_img, _ = self.texture_b512(x_spade, img_256, styles[-1], pose_feat, cat_feat, parsing_index, force_fp32=not self._half_on(self.texture_b512, ws),
                                                styles=pre['texture'] if pre is not None else None, **block_kwargs)
         return img, finetune_img, pred_parsing
 
@@ -1758,6 +1823,12 @@ class GeneratorFull_v20(nn.Module):
         self.mapping = MappingNetwork(z_dim=z_dim, c_dim=c_dim, w_dim=w_dim, num_ws=self.num_ws, **mapping_kwargs)
         self.const_encoding = ConstEncoderNetwork(input_nc=3 + 2, output_nc=512, ngf=64, n_downsampling=6)
         self.style_encoding = StyleEncoderNetworkV18(input_nc=(10 * 3 + 5 * 3), output_nc=512, ngf=64, n_downsampling=6)
+
+    def set_half(self, dtype, from_res=64):
+        """`SynthesisNetworkFull_v18.set_half`: the synthesis blocks at resolution >= `from_res` in bf16 / fp16 on the GPU's inference route (None: float32);
+        mapping and both encoders stay float32.  Returns self."""
+        self.synthesis.set_half(dtype, from_res=from_res)
+        return self
 
     def forward(self, z, c, retain, pose, denorm_upper_input, denorm_lower_input, denorm_upper_mask, denorm_lower_mask,
                 gt_parsing=None, truncation_psi=1, truncation_cutoff=None, **synthesis_kwargs):

@@ -271,6 +271,7 @@ class _Raw(_Unrouted):
 
 
 FRONTS = ('host', 'native')
+PRECISIONS = {'fp32': None, 'bf16': torch.bfloat16, 'fp16': torch.float16}
 
 
 def result_name(person_name, clothes_name):
@@ -283,15 +284,28 @@ def _write_png(path, rgb):
     PIL.Image.fromarray(rgb, 'RGB').save(path, compress_level=1)
 
 
-def run_tryon(dataset, G, outdir, batch_size=1, device='cuda', workers=0, stats=None, front='host'):
+def run_tryon(dataset, G, outdir, batch_size=1, device='cuda', workers=0, stats=None, front='host', precision='fp32'):
     """Try every pair of `dataset` (a ``TryOnTestSet``; its ``part`` picks the mode) on generator `G`, writing one PNG per pair into `outdir`.
     Returns the list of files written, in pair order.  `front` picks who builds the pre-routing maps: 'host' -- the loader's workers
     (``TryOnTestSet.unrouted``); 'native' -- the workers only decode (``TryOnTestSet.raw``) and ``tryon_front.front_batch`` builds the maps on the
     device, between the upload and the routing (same images, byte for byte).  `stats`, a dict, receives per-batch host seconds waiting for the
     loader ('load_s'), and on a GPU per-batch CUDA events ('events': (start, routed, inputs, generated, packed) per batch; with the native front
-    (start, front, routed, inputs, generated, packed)) -- read them after the call."""
+    (start, front, routed, inputs, generated, packed)) -- read them after the call.  `precision`: 'fp32' -- the reference's arithmetic --, or 'bf16' / 'fp16':
+    the generator's blocks from 64^2 up run in that type for this call (``GeneratorFull_v20.set_half``; GPU only, a CPU run computes in float32 whatever
+    it says); the generator's own setting is put back afterwards."""
     if front not in FRONTS:
         raise ValueError(f'front must be one of {FRONTS}, not {front!r}')
+    if precision not in PRECISIONS:
+        raise ValueError(f'precision must be one of {tuple(PRECISIONS)}, not {precision!r}')
+    before = (G.synthesis.half_dtype, G.synthesis.half_from_res)
+    G.set_half(PRECISIONS[precision])
+    try:
+        return _run_tryon(dataset, G, outdir, batch_size, device, workers, stats, front)
+    finally:
+        G.set_half(*before)
+
+
+def _run_tryon(dataset, G, outdir, batch_size, device, workers, stats, front):
     native = front == 'native'
     if native:
         from . import tryon_front
@@ -379,6 +393,8 @@ def parse_args(argv=None):
     p.add_argument('--outdir', required=True, help='where the PNGs go')
     p.add_argument('--device', default='cuda', help="'cuda', 'cuda:<i>' or 'cpu' (plain torch and NumPy)")
     p.add_argument('--workers', type=int, default=0, help='DataLoader worker processes (the reference uses 0)')
+    p.add_argument('--precision', choices=sorted(PRECISIONS), default='fp32', help="arithmetic of the generator's blocks from 64x64 up on a GPU: 'fp32' (the "
+                   "reference's), 'bf16' (recommended 16-bit type) or 'fp16'")
     p.add_argument('--front', choices=FRONTS, default='host', help="who builds the pre-routing maps: the loader's workers ('host') or the device "
                    "('native': the workers only decode the files)")
     # accepted for the reference's command lines; the reference ignores them for try-on, and so does this driver
@@ -398,6 +414,7 @@ def main(argv=None):
     print(f'Loading networks from "{args.network}"...')
     G = build_generator(args.network, args.device)
     dataset = ds_mod.TryOnTestSet(args.dataroot, test_txt=args.testtxt, use_sleeve_mask=args.use_sleeve_mask, part=args.testpart)
-    files = run_tryon(dataset, G, args.outdir, batch_size=args.batchsize, device=args.device, workers=args.workers, front=args.front)
+    files = run_tryon(dataset, G, args.outdir, batch_size=args.batchsize, device=args.device, workers=args.workers, front=args.front,
+                      precision=args.precision)
     print(f'wrote {len(files)} images to {args.outdir}')
     return files
