@@ -7,7 +7,7 @@
  *   bias_act_plugin.so      pg_bias_act
  *   upfirdn2d_plugin.so     pg_upfirdn2d, pg_upfirdn2d_bias_act, pg_upfirdn2d_with_odd_samples
  *   conv2d_plugin.so        fp32: pg_conv2d_{packed_size,pack_weight,forward,splitk_plan,forward_splitk}, pg_conv2d_winograd_*,
- *                           pg_conv2d_up2_{forward,splitk_plan,forward_splitk}, pg_conv1x1_small, pg_conv1x1_fold_{prep,heads}, pg_conv3x3_cin1, pg_conv2d_wgrad{_plan,}, pg_split3_bf16_cl;
+ *                           pg_conv2d_up2_{forward,splitk_plan,forward_splitk}, pg_conv1x1_small, pg_conv1x1_fold_{prep,heads}, pg_conv3x3_fold_head, pg_conv3x3_cin1, pg_conv2d_wgrad{_plan,}, pg_split3_bf16_cl;
  *                           16-bit: pg_conv2d16_{packed_size,pack_weight,pack_weight_grouped,forward,splitk_plan,forward_splitk,up2_fused,wgrad,wgrad_plan,wgrad_x3}, pg_adam_flat_{chunk,step},
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 16
+#define PG_ABI_VERSION 17
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -347,6 +347,17 @@ int pg_conv1x1_fold_prep(const float* wm, const float* bm, const float* wh, cons
                          int N, int Cm, int C, int Cout, void* stream);
 int pg_conv1x1_fold_heads(const float* x, const float* x2, const float* w, const float* bias, const float* skip, float* y_a, float* y_b,
                           int N, int C1, int C2, int64_t HW, int Cout, int c_a, int n_skip, float clamp, void* stream);
+
+/* Folded tail: a bias-free linear 3x3 convolution (padding 1) of xa plus a bias-free linear 1x1 convolution of xb, read only by a modulated linear 1x1 head,
+ * is one linear map of (xa, xb) per sample (csrc/conv3x3_fold.hip); the sum of the two convolutions is never written.
+ *   r[n,o,y,x] = clamp(sum_{c < C} sum_{ky,kx < 3} xa[n,c,y+ky-1,x+kx-1] * w[n,o,9c+3ky+kx] + sum_{c < C} xb[n,c,y,x] * w[n,o,9C+c] + bias[n,o]) (+ skip[n,o,y,x])
+ * xa, xb [N, C, H, W]; w [N, Cout, 10 C] (pg_conv1x1_fold_prep over wm = [3x3 weight as [Cm, 9 C] | 1x1 weight [Cm, C]], cross-correlation as F.conv2d);
+ * bias [N, Cout]; skip [N, Cout, H, W] or NULL; y [N, Cout, H, W]; samples of xa outside the image read as zero; clamp < 0 disables it.  One pass over xa
+ * and xb with 16-byte loads, a fixed summation order, no atomics.
+ * float32 dense NCHW, Cout <= 4, W % 4 == 0, 16-byte aligned tensors, H * W * 4 bytes <= 512 MB; PG_ERR_UNSUPPORTED otherwise (run the layers one after
+ * the other). */
+int pg_conv3x3_fold_head(const float* xa, const float* xb, const float* w, const float* bias, const float* skip, float* y,
+                         int N, int C, int H, int W, int Cout, float clamp, void* stream);
 
 /* 3x3 convolution of a one-channel image (first layer of the SPADE blocks on the parsing / mask map, networks.py:1708-1712):
  * y = act(conv2d(x [N,1,H,W], w [Cout,1,3,3] * scale, padding=1)), cross-correlation as F.conv2d; act = PG_ACT_LINEAR | PG_ACT_RELU

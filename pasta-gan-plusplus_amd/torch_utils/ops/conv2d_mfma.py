@@ -160,6 +160,8 @@ def _init(plugin_name='conv2d_plugin'):
         lib.pg_conv1x1_fold_prep.argtypes = [vp] * 7 + [i, i, i, i, vp]
         lib.pg_conv1x1_fold_heads.restype = i
         lib.pg_conv1x1_fold_heads.argtypes = [vp] * 7 + [i, i, i, i64, i, i, i, f, vp]
+        lib.pg_conv3x3_fold_head.restype = i
+        lib.pg_conv3x3_fold_head.argtypes = [vp] * 6 + [i, i, i, i, i, f, vp]
         _plugin = plugin
     return _plugin
 
@@ -787,6 +789,33 @@ def conv1x1_fold_heads(x, x2, w, b, c_a, skip=None, clamp=None):
                                        n_skip, float(clamp) if clamp is not None else -1.0, nat.stream_of(x))
     nat.check(rc, 'pg_conv1x1_fold_heads')
     return ya, yb
+
+
+def conv3x3_fold_ok(xa, xb, skip=None):
+    """Shapes the folded-tail kernel takes (csrc/conv3x3_fold.hip): two float32 dense NCHW inputs of one shape (the entry point itself declines a
+    width that is no multiple of 4)."""
+    return (xa.dtype == torch.float32 and xa.is_cuda and xa.is_contiguous() and xb.dtype == torch.float32 and xb.is_cuda and xb.is_contiguous()
+            and xa.shape == xb.shape
+            and (skip is None or (skip.dtype == torch.float32 and skip.is_cuda and skip.is_contiguous() and skip.shape[0] == xa.shape[0] and skip.shape[2:] == xa.shape[2:])))
+
+
+def conv3x3_fold_head(xa, xb, w, b, skip=None, clamp=None):
+    """clamp(conv3x3(xa, w[n][:, :9C], padding=1) + conv1x1(xb, w[n][:, 9C:]) + b[n]) (+ skip) in one streaming pass over xa and xb: w [N, Cout, 10 C] with
+    the 3x3 taps of channel c at [9c, 9c + 9) and its 1x1 weight at 9C + c, b [N, Cout] (`conv1x1_fold_prep`).  Returns y [N, Cout, H, W].  Raises
+    NativeNotCovered for shapes the kernel declines."""
+    lib = _init().lib
+    xa, xb, w, b, skip = _f32c(xa, 'xa'), _f32c(xb, 'xb'), _f32c(w, 'w'), _f32c(b, 'b'), _f32c(skip, 'skip')
+    n, c, h, wd = xa.shape
+    cout = int(w.shape[1])
+    if (tuple(xb.shape) != (n, c, h, wd) or tuple(w.shape) != (n, cout, 10 * c) or tuple(b.shape) != (n, cout)
+            or (skip is not None and tuple(skip.shape) != (n, cout, h, wd))):
+        raise nat.NativeOpError('conv3x3_fold_head: xa, xb [N, C, H, W], w [N, Cout, 10 C], b [N, Cout], skip [N, Cout, H, W]')
+    y = torch.empty([n, cout, h, wd], dtype=torch.float32, device=xa.device)
+    with torch.cuda.device(xa.device):
+        rc = lib.pg_conv3x3_fold_head(nat.ptr(xa), nat.ptr(xb), nat.ptr(w), nat.ptr(b), nat.ptr(skip), nat.ptr(y), n, c, h, wd, cout,
+                                      float(clamp) if clamp is not None else -1.0, nat.stream_of(xa))
+    nat.check(rc, 'pg_conv3x3_fold_head')
+    return y
 
 
 def modconv_dcoefs(weight, styles, scale=1.0):

@@ -1080,20 +1080,29 @@ class Spade_ResBlockV4_512(nn.Module):
         self.spade0 = Spade_Norm_Block(spade_channels, in_channels)
         self.spade1 = Spade_Norm_Block(spade_channels, out_channels)
 
-    def forward(self, x, denorm_feat):
+    def forward(self, x, denorm_feat, _defer_tail=False):
+        """`_defer_tail` (private): on the float32 inference route stop in front of the linear tail `conv1(h') + skip(s')` and return (h', s') -- the two SPADE
+        outputs, each with its consumer's pre-activation applied -- for a caller that folds the tail into what reads it (`tail` finishes it otherwise)."""
         if (_fast_ok(x, denorm_feat, self.conv.weight, self.conv0.weight) or _fast16_ok(x, denorm_feat, self.conv.weight, self.conv0.weight)) and all(l.bias is None and l.activation in conv2d_mfma.FUSED_ACTS for l in (self.skip, self.conv0, self.conv1)):
             # inference route: each SPADE output feeds exactly one convolution, so that convolution's pre-activation is applied
             # where the SPADE output is produced and the convolutions run without a prologue; the statistics the norm blocks need come out of
             # the tail of the convolution that produces their input (round 4: no second pass over x / dx)
             assert self.spade_skip.param_free_norm.eps == self.spade0.param_free_norm.eps
             x, stats = self.conv(x, no_act=True, stats_eps=self.spade0.param_free_norm.eps)       # spade_skip and spade0 normalise the same x
-            y = self.skip(self.spade_skip(x, denorm_feat, post=self.skip.pre_activation(SQRT_HALF), stats=stats), no_act=True)
+            s = self.spade_skip(x, denorm_feat, post=self.skip.pre_activation(SQRT_HALF), stats=stats)
+            defer = _defer_tail and s.dtype == torch.float32
+            y = None if defer else self.skip(s, no_act=True)
             x, stats1 = self.conv0(self.spade0(x, denorm_feat, post=self.conv0.pre_activation(), stats=stats), no_act=True, stats_eps=self.spade1.param_free_norm.eps)
-            return self.conv1(self.spade1(x, denorm_feat, post=self.conv1.pre_activation(SQRT_HALF), stats=stats1), no_act=True, residual=y)
+            h = self.spade1(x, denorm_feat, post=self.conv1.pre_activation(SQRT_HALF), stats=stats1)
+            return (h, s) if defer else self.conv1(h, no_act=True, residual=y)
         x = self.conv(x, no_act=True)
         y = self.skip(self.spade_skip(x, denorm_feat), gain=SQRT_HALF)
         x = self.conv0(self.spade0(x, denorm_feat))
         return self.conv1(self.spade1(x, denorm_feat), gain=SQRT_HALF, residual=y)
+
+    def tail(self, h, s):
+        """The tail a `_defer_tail` call left out: conv1(h') + skip(s'), the launches of the undeferred inference route."""
+        return self.conv1(h, no_act=True, residual=self.skip(s, no_act=True))
 
 
 class SynthesisLayer(nn.Module):
@@ -1323,9 +1332,58 @@ class _SynthesisBlockBase(nn.Module):
         rgb, pred_parsing = self.torgb(x, w, fused_modconv=fused_modconv, skip_img=img, styles=styles)
         return x, rgb, pred_parsing
 
+    def _tail_fold_ok(self):
+        """The layer properties under which the texture block's tail folds into its ToRGB head (`_tail_folded`): spade_b512 ends with a bias-free 3x3
+        (padding 1) plus a bias-free 1x1, both without resampling, and the only head is a 1x1 ToRGB.  PG_TEX_FOLD=0: never (A/B runs)."""
+        sb, tr = getattr(self, 'spade_b512', None), getattr(self, 'torgb', None)
+        if sb is None or tr is None or not self.TEXTURE or torch.is_grad_enabled() or os.environ.get('PG_TEX_FOLD', '1') == '0':
+            return False
+        c1, sk = sb.conv1, sb.skip
+        cm = int(tr.weight.shape[1])
+        return (all(l.bias is None and l.up == 1 and l.down == 1 and int(l.weight.shape[0]) == cm for l in (c1, sk))
+                and tuple(c1.weight.shape[2:]) == (3, 3) and c1.padding == 1 and tuple(sk.weight.shape[2:]) == (1, 1) and sk.padding == 0
+                and c1.weight.shape[1] == sk.weight.shape[1] and tuple(tr.weight.shape[2:]) == (1, 1) and not (tr.is_last and tr.is_style))
+
+    def _tail_folded(self, h, s, w, styles, img):
+        """fp32 inference, texture block: the tail of spade_b512, conv1(h') + skip(s') (both linear and bias-free, so zero padding stays exact), and the ToRGB
+        head behind it are one linear map of (h', s') per sample with 3 x C x 9 + 3 x C weights; one streaming pass over h' and s' computes the image without
+        the block's feature map (csrc/conv3x3_fold.hip).  Returns rgb, or None where the kernel does not cover the call (the caller then runs the layers one
+        after the other)."""
+        sb, tr = self.spade_b512, self.torgb
+        c1, sk = sb.conv1, sb.skip
+        params = [c1.weight, sk.weight, tr.weight, tr.bias]
+        if not (_fast_ok(h, s, styles, img, tr.affine.weight, tr.affine.bias, *params) and conv2d_mfma.conv3x3_fold_ok(h, s, img)):
+            return None
+
+        def build():
+            cm = int(c1.weight.shape[0])
+            return (torch.cat([(c1.weight.detach().float() * c1.weight_gain).reshape(cm, -1), (sk.weight.detach().float() * sk.weight_gain).reshape(cm, -1)], dim=1).contiguous(),
+                    tr.weight.detach().float().reshape(tr.weight.shape[0], cm).contiguous(), tr.bias.detach().float().contiguous())
+        wm, wh, bh = self._fold_cache.get(('tail',), params, build)
+        if styles is None:
+            styles = tr.affine(w) * tr.weight_gain
+        try:
+            wn, bn = conv2d_mfma.conv1x1_fold_prep(wm, None, wh, bh, styles)
+            return conv2d_mfma.conv3x3_fold_head(h, s, wn, bn, skip=img, clamp=tr.conv_clamp)
+        except nat.NativeNotCovered:
+            return None
+
+    def _spade_heads(self, x, parsing, w, styles, img, fused_modconv, feat_unused=False):
+        """spade_b512 over x, then img + ToRGB: (x, rgb, pred_parsing).  `feat_unused`: nothing reads the SPADE block's result but the head -- its tail is
+        then not computed where `_tail_folded` covers the call, and x comes back as None."""
+        x = self.spade_b512(x, parsing, _defer_tail=feat_unused and self._tail_fold_ok())
+        if isinstance(x, tuple):
+            rgb = self._tail_folded(*x, w, styles, img)
+            if rgb is not None:
+                return None, rgb, None
+            x = self.spade_b512.tail(*x)
+        rgb, pred_parsing = self.torgb(x, w, fused_modconv=fused_modconv, skip_img=img, styles=styles)
+        return x, rgb, pred_parsing
+
     def _forward(self, x, img, ws, pose_feature, cat_feat, parsing, force_fp32, fused_modconv, styles=None, _feat_unused=False, **layer_kwargs):
         """`styles` (private): the block's affine outputs in `affine_layers()` order when the network computed them for all layers at once.
-        `_feat_unused` (private): the caller does not read the returned feature map (the network's last style block); it may come back as None."""
+        `_feat_unused` (private): the caller does not read the returned feature map (the network's last style block, the texture block); it may come back
+        as None."""
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
         half = (self.use_fp16 or self.half_dtype is not None) and not force_fp32
         fmt = dict(dtype=(self.half_dtype or torch.float16) if half else torch.float32,
@@ -1358,6 +1416,14 @@ class _SynthesisBlockBase(nn.Module):
                         return x, rgb.to(dtype=torch.float32, memory_format=torch.contiguous_format), pred_parsing
                     x = self.merge_conv(x, x2=feat)
                 if self.TEXTURE:
+                    if _feat_unused and self.has_torgb and not half:
+                        # the SPADE block's result feeds only the image head: the head is computed from the block's two last SPADE outputs directly where
+                        # the folded kernel covers the call
+                        if img is not None:
+                            misc.assert_shape(img, [None, self.img_channels, self.resolution // 2, self.resolution // 2])
+                            img = upfirdn2d.upsample2d(img, self.resample_filter)
+                        x, rgb, pred_parsing = self._spade_heads(x, parsing, style(self.num_conv), st[self.num_conv], img, fused_modconv, feat_unused=True)
+                        return x, rgb.to(dtype=torch.float32, memory_format=torch.contiguous_format), pred_parsing
                     x = self.spade_b512(x, parsing)
 
         if img is not None:
@@ -1383,8 +1449,8 @@ class SynthesisBlockFull_v1_v4(_SynthesisBlockBase):
     TORGB = ToRGBLayerFull_v1_v4
     TEXTURE = True
 
-    def forward(self, x, img, ws, pose_feature, cat_feat, parsing, force_fp32=False, fused_modconv=None, styles=None, **layer_kwargs):
-        return self._forward(x, img, ws, pose_feature, cat_feat, parsing, force_fp32, fused_modconv, styles=styles, **layer_kwargs)
+    def forward(self, x, img, ws, pose_feature, cat_feat, parsing, force_fp32=False, fused_modconv=None, styles=None, _feat_unused=False, **layer_kwargs):
+        return self._forward(x, img, ws, pose_feature, cat_feat, parsing, force_fp32, fused_modconv, styles=styles, _feat_unused=_feat_unused, **layer_kwargs)
 
 
 def _half_nearest(t):
@@ -1567,8 +1633,9 @@ class SynthesisNetworkFull_v18(nn.Module):
         if x_256.dtype != torch.float32:       # half mode: the 128-channel garment features are cast once for the six norm blocks that read them
             spade_feat = spade_feat.to(dtype=x_256.dtype, memory_format=torch.channels_last)
         x_spade = self.spade_b256_2(self.spade_b256_1(x_256, spade_feat), spade_feat)
+        # (the texture block's feature map is read by nobody: the block may fold the tail of its SPADE block into its image head)
         _, finetune_img, _ = self.texture_b512(x_spade, img_256, styles[-1], pose_feat, cat_feat, parsing_index, force_fp32=not self._half_on(self.texture_b512, ws),
-                                               styles=pre['texture'] if pre is not None else None, **block_kwargs)
+                                               styles=pre['texture'] if pre is not None else None, _feat_unused=True, **block_kwargs)
         return img, finetune_img, pred_parsing
 
 
