@@ -15,6 +15,7 @@
  *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8
  *   train_fetch_plugin.so   pg_train_fetch
  *   tryon_front_plugin.so   pg_tryon_front_stats, pg_tryon_front_bit_rows, pg_tryon_front_compose
+ *   vgg_loss_plugin.so      pg_maxpool2x2, pg_maxpool2x2_backward, pg_l1_pair_blocks, pg_l1_pair_sum, pg_l1_pair_grad
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -778,6 +779,23 @@ int pg_tryon_front_stats(const pg_front_io* io, int n, int H, int W, void* strea
 int pg_tryon_front_bit_rows(const pg_front_io* io, int n, int H, int W, int left, int mode, void* stream);
 int pg_tryon_front_compose(const pg_front_io* io, int n, int H, int W, int left, int mode, void* stream);
 int pg_tryon_front_abi_version(void);
+
+/* vgg_loss_plugin.so -- the non-convolution operators of the VGG19 perceptual loss (training/vgg_loss.py).  float32, dense NCHW; `planes` = n * c.
+ * No atomics (bit-identical run to run), nothing read to the host, no allocation.
+ * pg_maxpool2x2: y [planes, h/2, w/2] = max over the 2x2 windows of x [planes, h, w] (nn.MaxPool2d(2, 2): a trailing odd row / column is dropped);
+ *   aten's scan: row-major from -inf, an element replaces the maximum when it is greater or NaN.  h, w >= 2.
+ * pg_maxpool2x2_backward: dx [planes, h, w] = dy routed to the element that scan picks (recomputed from x), 0 elsewhere; EVERY element of dx is written.
+ * pg_l1_pair_sum: x = `groups` tensors of m elements each, stacked; y = one tensor of m elements, read once for all groups.
+ *   out[g] = scale * sum_i |x[g][i] - y[i]|.  `partials` = workspace of groups * pg_l1_pair_blocks(m) floats (need not be initialised).  Two launches.
+ * pg_l1_pair_grad: dx[g][i] = sgn(x[g][i] - y[i]) * (s[g] / (float)denom); sgn(0) = 0; `s` = `groups` device floats. */
+#define PG_L1_PAIR_MAX_GROUPS 8
+#define PG_L1_PAIR_MAX_BLOCKS 1024
+int pg_maxpool2x2(const float* x, float* y, int64_t planes, int h, int w, void* stream);
+int pg_maxpool2x2_backward(const float* x, const float* dy, float* dx, int64_t planes, int h, int w, void* stream);
+int pg_l1_pair_blocks(int64_t m);
+int pg_l1_pair_sum(const float* x, const float* y, float* partials, float* out, int groups, int64_t m, double scale, void* stream);
+int pg_l1_pair_grad(const float* x, const float* y, const float* s, float* dx, int groups, int64_t m, double denom, void* stream);
+int pg_vgg_loss_abi_version(void);
 
 #ifdef __cplusplus
 }

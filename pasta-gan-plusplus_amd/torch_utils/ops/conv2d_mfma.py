@@ -7,6 +7,7 @@ native layer under this package's ``conv2d_gradfix`` / ``conv2d_resample`` /
 ``training.networks``; forward only (gradients are attached in ``conv2d_gradfix``).
 """
 
+import contextlib
 import ctypes
 import os
 
@@ -199,6 +200,25 @@ def f4_form(hw):
     return F4_FORM if int(hw[1]) < 64 else F4_WIDE
 
 
+_algo_override = []      # innermost `algo(...)` last
+
+
+@contextlib.contextmanager
+def algo(mode):
+    """The launch policy of `use_winograd` for the convolutions called inside the block, as PG_CONV_ALGO would set it ('auto', 'direct', 'winograd',
+    'winograd2', 'winograd4'); None changes nothing.  It holds for the calls made inside it only: a backward pass that runs after the block is under
+    whatever holds then."""
+    if mode is None:
+        yield
+        return
+    assert mode in ('auto', 'direct', 'winograd', 'winograd2', 'winograd4')
+    _algo_override.append(mode)
+    try:
+        yield
+    finally:
+        _algo_override.pop()
+
+
 def use_winograd(kh, kw, stride, cout, cin=None, x2=None, pad=None, hw=None, xf=False, ep=None):
     """Launch policy for 3x3 stride-1 convolutions.  Returns 0 (direct implicit GEMM), WINO_F2 (Winograd F(2x2,3x3), csrc/conv2d_wino.h) or one of
     the three F(4x4,3x3) forms (`f4_form`: WINO_F4B, csrc/conv2d_wino4b.h, for images narrower than 64 pixels, WINO_F4X3 -- or WINO_F4 under PG_WINO4_X3=0 --
@@ -213,7 +233,7 @@ def use_winograd(kh, kw, stride, cout, cin=None, x2=None, pad=None, hw=None, xf=
         return 0
     if pad is not None and not 0 <= int(pad[1]) <= 4:         # the kernels' LDS halo row starts 4 columns left of the tile
         return 0
-    mode = os.environ.get('PG_CONV_ALGO', 'auto')
+    mode = _algo_override[-1] if _algo_override else os.environ.get('PG_CONV_ALGO', 'auto')
     if mode == 'direct':
         return 0
     f4_possible = hw is not None and not xf and int(hw[1]) % 4 == 0 and (pad is None or (int(hw[1]) + 2 * int(pad[1]) - 2) % 4 == 0)

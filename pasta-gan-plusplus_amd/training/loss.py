@@ -3,10 +3,10 @@
 (coarse image, fine-tuned image, predicted parsing), L1 to the real image, class-weighted cross-entropy
 on the parsing head, and lazy R1 on both discriminators.
 
-Not restated: the VGG perceptual and contextual terms (:336-618) -- their weights
-(``./checkpoints/vgg19*.pth``) are not available offline (``train.sh`` runs with contextual_weight 0);
-pass ``vgg_weight=0`` semantics are the only ones supported.  Path-length regularisation is commented out
-in the reference (:200-221), so a ``Greg`` phase only runs the style encoder.
+The VGG19 perceptual term (:178-193, :336-386) is on with ``vgg_weight > 0`` and a ``training.vgg_loss.VGGLoss`` passed as ``vgg``: its
+weights come from a checkpoint that is not shipped (``./checkpoints/vgg19-dcbb9e9d.pth`` in the reference), so without one the term is
+refused.  Not restated: the contextual term (:487-618), which the reference never calls (``train.sh`` runs with contextual_weight 0).
+Path-length regularisation is commented out in the reference (:200-221), so a ``Greg`` phase only runs the style encoder.
 
 Gradient synchronisation is NOT done here (the reference toggles DDP's hooks through ``ddp_sync``, letting only the
 LAST backward of the last accumulation round reduce): ``on_last_backward``, when set, is called right before that
@@ -25,9 +25,12 @@ _G_PARTS = ('G_mapping', 'G_synthesis', 'G_const_encoding', 'G_style_encoding')
 class StyleGAN2Loss:
     def __init__(self, device, G_mapping, G_synthesis, G_const_encoding, G_style_encoding, D, D_parsing, augment_pipe=None,
                  style_mixing_prob=0.9, r1_gamma=10, pl_batch_shrink=2, pl_decay=0.01, pl_weight=0, l1_weight=50, vgg_weight=0,
-                 contextual_weight=0, mask_weight=1.0, report=None):
-        if vgg_weight or contextual_weight:
-            raise NotImplementedError('VGG / contextual terms need checkpoints that are not available offline')
+                 contextual_weight=0, mask_weight=1.0, report=None, vgg=None):
+        if contextual_weight:
+            raise NotImplementedError('the contextual term is not restated (the reference never calls it)')
+        if vgg_weight and vgg is None:
+            raise NotImplementedError('vgg_weight > 0 needs a checkpoint: pass vgg=VGGLoss(VGG19Features(load_vgg19(path))) (training/vgg_loss.py)')
+        self.vgg_weight, self.vgg = vgg_weight, (vgg if vgg_weight else None)
         self.device = device
         self.G_mapping, self.G_synthesis, self.G_const_encoding, self.G_style_encoding = G_mapping, G_synthesis, G_const_encoding, G_style_encoding
         self.D, self.D_parsing, self.augment_pipe = D, D_parsing, augment_pipe
@@ -103,6 +106,11 @@ class StyleGAN2Loss:
             if self.mask_weight > 0:
                 ce = F.cross_entropy(pred_parsing, gt_parsing.long()[:, 0], weight=self.class_weight, ignore_index=255) * self.mask_weight
             loss_G = adv + l1 + ce + adv_parsing
+            if self.vgg is not None:                                 # loss_fullbody.py:178-193; the real image's features are computed once for both
+                vgg, vgg_fine = (self.vgg([gen_img, gen_fine], real_img) * self.vgg_weight).unbind(0)
+                loss_G = loss_G + (vgg + vgg_fine) / 2
+                self.report('Loss/G/vgg', vgg)
+                self.report('Loss/G/vgg_finetune', vgg_fine)
             self.report('Loss/G/loss', adv)
             self.report('Loss/G/L1', l1)
             self.report('Loss/G/mask_loss', ce)

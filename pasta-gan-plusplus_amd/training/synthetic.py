@@ -76,3 +76,25 @@ def synthesis_inputs(n, w_dim=512, num_ws=14, feat_ch=512, seed_tag='cfg2', labe
         gt_parsing=det_tensor(f'{t}.parsing', [n, 1, 512, 512], 'labels7') if labels else None,
     )
     return inp
+
+
+# torchvision's vgg19 (configuration "E"): index in `features` -> (Cin, Cout) of its sixteen 3x3 convolutions
+VGG19_CONVS = {0: (3, 64), 2: (64, 64), 5: (64, 128), 7: (128, 128), 10: (128, 256), 12: (256, 256), 14: (256, 256), 16: (256, 256),
+               19: (256, 512), 21: (512, 512), 23: (512, 512), 25: (512, 512), 28: (512, 512), 30: (512, 512), 32: (512, 512), 34: (512, 512)}
+VGG19_CLASSIFIER = {0: (4096, 512 * 7 * 7), 3: (4096, 4096), 6: (1000, 4096)}
+
+
+def vgg19_state_dict(classifier=False):
+    """A torchvision-format VGG19 state dict of name-keyed values at the real widths (the pretrained ``vgg19-dcbb9e9d.pth`` is not available
+    offline): weights ~ N(0, 2 / (9 Cin)) (He: activations keep their scale through thirteen ReLU layers), biases ~ 0.05 N(0, 1).
+    `classifier=True` adds zero ``classifier.*`` entries, as a strict ``load_state_dict`` of the whole network wants them: zero-stride views of
+    one zero, so that a saved checkpoint stays small."""
+    sd = {}
+    for idx, (cin, cout) in VGG19_CONVS.items():
+        sd[f'features.{idx}.weight'] = det_tensor(f'vgg19.features.{idx}.weight', [cout, cin, 3, 3], scale=(2.0 / (9 * cin)) ** 0.5)
+        sd[f'features.{idx}.bias'] = det_tensor(f'vgg19.features.{idx}.bias', [cout], scale=0.05)
+    if classifier:
+        for idx, (cout, cin) in VGG19_CLASSIFIER.items():
+            sd[f'classifier.{idx}.weight'] = torch.zeros([]).expand(cout, cin)
+            sd[f'classifier.{idx}.bias'] = torch.zeros([]).expand(cout)
+    return sd

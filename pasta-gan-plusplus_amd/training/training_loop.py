@@ -6,8 +6,9 @@ module builds the networks, runs the two until `kimg`, prints the reference's st
 
 Snapshots are plain ``torch.save`` dicts of ``state_dict``s under the reference's parameter names -- ``G``, ``D``, ``D_parsing``, ``G_ema``,
 ``augment_p``, ``cur_nimg`` -- which ``--resume`` reads back; ``--resume`` also reads a reference snapshot (.pkl) through ``checkpoint.load_into``
-(nothing in it is executed).  Writing the reference's own pickle format is out of scope (its pickles embed module source), as are the VGG /
-contextual terms, metrics, zip datasets and tensorboard."""
+(nothing in it is executed).  The VGG19 perceptual term (``vgg_weight`` > 0) needs ``vgg_ckpt``, a torchvision-format ``vgg19`` state dict
+(training/vgg_loss.py); its tensors are buffers of the loss, in no snapshot.  Writing the reference's own pickle format is out of scope (its
+pickles embed module source), as are the contextual term, metrics, zip datasets and tensorboard."""
 
 import argparse
 import json
@@ -77,10 +78,17 @@ def image_interval(snap, image_snap):
 
 
 def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, mask_weight=1.0, vgg_weight=0, contextual_weight=0, aug='ada', target=0.6,
-                  seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None):
+                  seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None,
+                  vgg_ckpt=None):
     """Train on the dataset directory `data` for `kimg` thousand images (one process, one GPU: `batch` = `batch_gpu` x accumulation rounds).
     Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied.
-    `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none)."""
+    `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none).
+    `vgg_weight` > 0 turns the VGG19 perceptual term on and needs `vgg_ckpt` (no default path): NotImplementedError without one, FileNotFoundError for
+    a path that does not exist, both before any network is built."""
+    if vgg_weight and vgg_ckpt is None:
+        raise NotImplementedError('vgg_weight > 0 needs --vgg_ckpt: a torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth is not shipped)')
+    if vgg_weight and not os.path.isfile(vgg_ckpt):
+        raise FileNotFoundError(f'--vgg_ckpt "{vgg_ckpt}" does not exist')
     if batch % batch_gpu:
         raise ValueError('--batch must be a multiple of --batch-gpu')
     if aug not in ('ada', 'noaug'):
@@ -104,8 +112,12 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
     def report(name, value):
         if name.startswith('Loss/') and name != 'Loss/signs/real' and isinstance(value, torch.Tensor):      # (a phase reports 0 for a term it skips)
             sums.setdefault(name, []).append(value.detach().float().mean())
+    vgg = None
+    if vgg_weight:
+        from . import vgg_loss
+        vgg = vgg_loss.VGGLoss(vgg_loss.VGG19Features(vgg_loss.load_vgg19(vgg_ckpt))).to(dev)
     loss = StyleGAN2Loss(device=dev, **parts, D=D, D_parsing=D_parsing, style_mixing_prob=0.9, r1_gamma=gamma, l1_weight=l1_weight, vgg_weight=vgg_weight,
-                         contextual_weight=contextual_weight, mask_weight=mask_weight, report=report)
+                         vgg=vgg, contextual_weight=contextual_weight, mask_weight=mask_weight, report=report)
     pipe = augment.AugmentPipe(**augment.AUGPIPE_SPECS['bgc']).to(dev) if aug == 'ada' else None
     step = TrainingStep(parts, D, D_parsing, loss, batch_size=batch, G_ema_parts=g_parts(G_ema), augment_pipe=pipe,
                         augment_p=augment_p if augment_p is not None else 0, ada_target=target if aug == 'ada' else None)
@@ -167,7 +179,8 @@ def parse_args(argv=None):
     p.add_argument('--gamma', type=float, default=10, help='R1 weight')
     p.add_argument('--l1_weight', type=float, default=50)
     p.add_argument('--mask_weight', type=float, default=1.0)
-    p.add_argument('--vgg_weight', type=float, default=0, help='only 0 is supported')
+    p.add_argument('--vgg_weight', type=float, default=0, help='weight of the VGG19 perceptual term (the reference\'s train.sh: 20); > 0 needs --vgg_ckpt')
+    p.add_argument('--vgg_ckpt', default=None, help='torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth); no default path')
     p.add_argument('--contextual_weight', type=float, default=0, help='only 0 is supported')
     p.add_argument('--aug', choices=['ada', 'noaug'], default='ada')
     p.add_argument('--target', type=float, default=0.6, help='ADA target')
@@ -186,4 +199,4 @@ def main(argv=None):
     a = parse_args(argv)
     return training_loop(a.outdir, a.data, batch=a.batch, batch_gpu=a.batch_gpu, gamma=a.gamma, l1_weight=a.l1_weight, mask_weight=a.mask_weight,
                          vgg_weight=a.vgg_weight, contextual_weight=a.contextual_weight, aug=a.aug, target=a.target, seed=a.seed, workers=a.workers,
-                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap)
+                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt)
