@@ -2,8 +2,8 @@
  * pasta_gan_ops.h -- C ABI of the MI355X (gfx950) kernels behind PASTA-GAN++'s
  * generator-synthesis operator API.
  *
- * Eight shared libraries export these symbols (one per reference "plugin", plus the loader's patch routing, the augment pipe, the try-on staging
- * and the training loop's data fetch):
+ * These shared libraries export the symbols below (one per reference "plugin", plus the loader's patch routing, the augment pipe, the try-on staging,
+ * the training loop's data fetch and the reconstruction metrics):
  *   bias_act_plugin.so      pg_bias_act
  *   upfirdn2d_plugin.so     pg_upfirdn2d, pg_upfirdn2d_bias_act, pg_upfirdn2d_with_odd_samples
  *   conv2d_plugin.so        fp32: pg_conv2d_{packed_size,pack_weight,forward,splitk_plan,forward_splitk}, pg_conv2d_winograd_*,
@@ -16,6 +16,7 @@
  *   train_fetch_plugin.so   pg_train_fetch
  *   tryon_front_plugin.so   pg_tryon_front_stats, pg_tryon_front_bit_rows, pg_tryon_front_compose
  *   vgg_loss_plugin.so      pg_maxpool2x2, pg_maxpool2x2_backward, pg_l1_pair_blocks, pg_l1_pair_sum, pg_l1_pair_grad
+ *   image_metrics_plugin.so pg_image_pair_metrics_workspace, pg_image_pair_metrics_u8
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -37,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 17
+#define PG_ABI_VERSION 18
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -796,6 +797,33 @@ int pg_l1_pair_blocks(int64_t m);
 int pg_l1_pair_sum(const float* x, const float* y, float* partials, float* out, int groups, int64_t m, double scale, void* stream);
 int pg_l1_pair_grad(const float* x, const float* y, const float* s, float* dx, int groups, int64_t m, double denom, void* stream);
 int pg_vgg_loss_abi_version(void);
+
+/* image_metrics_plugin.so -- the paired reconstruction metrics (torch_utils/ops/image_metrics.py, training/metrics.py, calc_metrics.py): per pair of
+ * uint8 images of one shape [h, w, channels] the exact sums sad = sum |a - b| and ssd = sum (a - b)^2 over all pixels and channels, and the mean
+ * SSIM (Wang et al. 2004: separable 11-tap Gaussian window, sigma 1.5, taps normalised; "valid" positions only, (h - 10)(w - 10) per channel;
+ * population moments; C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2; mean over positions and channels).  An image is a base pointer, a row stride and a
+ * pixel stride in elements (channel stride 1), so a pair may be two windows of one larger image; no byte outside a window is read, and nothing need be
+ * aligned.  No atomics (bit-identical run to run, and a pair's result does not depend on the other pairs of the call); nothing read to the host.
+ * The job table is given twice: `jobs_host` is read by the call itself (argument checks, grid size), `jobs_device` -- the same bytes in device
+ * memory -- by the kernels.  pg_image_pair_metrics_workspace: bytes of `workspace` for that table (need not be initialised), or a negative PG_ERR_*.
+ * pg_image_pair_metrics_u8: sad[j], ssd[j] (int64) and ssim[j] (float32) for j < npairs.  Two launches.  PG_ERR_INVALID_ARG for npairs <= 0, a NULL
+ *   table or pointer, h or w < 11, channels outside {1, 3}, pix_stride < channels or row_stride < 1; PG_ERR_TOO_LARGE for h * w * channels >= 2^31 or
+ *   npairs > PG_METRIC_MAX_PAIRS. */
+#define PG_METRIC_MAX_PAIRS 65535
+typedef struct pg_metric_pair {
+    const unsigned char* a;                /* first byte of window a */
+    const unsigned char* b;
+    int64_t a_row_stride;                  /* elements between rows */
+    int64_t b_row_stride;
+    int a_pix_stride;                      /* elements between pixels, >= channels */
+    int b_pix_stride;
+    int h, w, channels;
+    int pad_;
+} pg_metric_pair;
+int64_t pg_image_pair_metrics_workspace(const pg_metric_pair* jobs_host, int npairs);
+int pg_image_pair_metrics_u8(const pg_metric_pair* jobs_host, const pg_metric_pair* jobs_device, int npairs, void* workspace,
+                             int64_t* sad, int64_t* ssd, float* ssim, void* stream);
+int pg_image_metrics_abi_version(void);
 
 #ifdef __cplusplus
 }

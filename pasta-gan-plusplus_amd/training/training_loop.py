@@ -8,7 +8,9 @@ Snapshots are plain ``torch.save`` dicts of ``state_dict``s under the reference'
 ``augment_p``, ``cur_nimg`` -- which ``--resume`` reads back; ``--resume`` also reads a reference snapshot (.pkl) through ``checkpoint.load_into``
 (nothing in it is executed).  The VGG19 perceptual term (``vgg_weight`` > 0) needs ``vgg_ckpt``, a torchvision-format ``vgg19`` state dict
 (training/vgg_loss.py); its tensors are buffers of the loss, in no snapshot.  Writing the reference's own pickle format is out of scope (its
-pickles embed module source), as are the contextual term, metrics, zip datasets and tensorboard."""
+pickles embed module source), as are the contextual term, the reference's detector-based metrics (FID, KID, PR, PPL, IS), zip datasets and
+tensorboard.  ``metrics`` (``--metrics l1,psnr,ssim``) is opt-in: on image-snapshot ticks the reconstruction error of the grid's diagonal cells goes
+into ``stats.jsonl`` as ``Metric/recon_*`` (training/metrics.py)."""
 
 import argparse
 import json
@@ -79,16 +81,21 @@ def image_interval(snap, image_snap):
 
 def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, mask_weight=1.0, vgg_weight=0, contextual_weight=0, aug='ada', target=0.6,
                   seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None,
-                  vgg_ckpt=None):
+                  vgg_ckpt=None, metrics=None):
     """Train on the dataset directory `data` for `kimg` thousand images (one process, one GPU: `batch` = `batch_gpu` x accumulation rounds).
     Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied.
     `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none).
     `vgg_weight` > 0 turns the VGG19 perceptual term on and needs `vgg_ckpt` (no default path): NotImplementedError without one, FileNotFoundError for
-    a path that does not exist, both before any network is built."""
+    a path that does not exist, both before any network is built.  `metrics`: None, or names out of 'l1', 'psnr', 'ssim' -- each image-snapshot tick
+    then adds ``Metric/recon_<name>`` (training/metrics.py) to its ``stats.jsonl`` line and prints them after the status line."""
     if vgg_weight and vgg_ckpt is None:
         raise NotImplementedError('vgg_weight > 0 needs --vgg_ckpt: a torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth is not shipped)')
     if vgg_weight and not os.path.isfile(vgg_ckpt):
         raise FileNotFoundError(f'--vgg_ckpt "{vgg_ckpt}" does not exist')
+    metrics_mod = None
+    if metrics:
+        from . import metrics as metrics_mod
+        metrics = metrics_mod.parse_metrics(metrics)
     if batch % batch_gpu:
         raise ValueError('--batch must be a multiple of --batch-gpu')
     if aug not in ('ada', 'noaug'):
@@ -135,6 +142,8 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
             grid = snapshot_grid.setup_snapshot_grid(dataset, dev)
             for name, array in zip(('init_denorm_upper.png', 'init_denorm_lower.png'), grid.canvas_grids()):
                 snapshot_grid.save_png(os.path.join(run_dir, name), array)
+    if metrics and grid is None:
+        print('No image grid: --metrics is off.')
 
     print(f'Training for {kimg} kimg...\n')
     start_time = tick_start_time = time.time()
@@ -153,11 +162,18 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
                         f'sec/tick {tick_end_time - tick_start_time:<7.1f}',
                         f'sec/kimg {(tick_end_time - tick_start_time) / max(step.cur_nimg - tick_start_nimg, 1) * 1e3:<7.2f}',
                         f'maintenance {maintenance_time:<6.1f}', f'gpumem {gpumem:<6.2f}', f'augment {p_now:.3f}']), flush=True)
+        image_tick = grid is not None and (done or cur_tick % image_snap == 0)
+        rendered = None
+        if metrics and image_tick:                                # the grid is rendered before the stats line is written: its figures go into it
+            rendered = grid.render(G_ema, batch_gpu)
+            recon = metrics_mod.grid_reconstruction(grid, metrics)
+            means.update(recon)
+            print(' '.join(f'{k} {v:.6g}' for k, v in recon.items()), flush=True)
         with open(os.path.join(run_dir, 'stats.jsonl'), 'a') as f:
             f.write(json.dumps(dict(means, **{'Progress/tick': cur_tick, 'Progress/kimg': step.cur_nimg / 1e3, 'Progress/augment': p_now,
                                               'timestamp': time.time()})) + '\n')
-        if grid is not None and (done or cur_tick % image_snap == 0):
-            for name, array in zip(('finetune', 'parsing'), grid.render(G_ema, batch_gpu)):
+        if image_tick:
+            for name, array in zip(('finetune', 'parsing'), rendered if rendered is not None else grid.render(G_ema, batch_gpu)):
                 snapshot_grid.save_png(os.path.join(run_dir, f'fakes{step.cur_nimg // 1000:06d}_{name}.png'), array)
         if snap is not None and (done or cur_tick % snap == 0):
             save_snapshot(os.path.join(run_dir, f'network-snapshot-{step.cur_nimg // 1000:06d}.pt'), G, D, D_parsing, G_ema, p_now, step.cur_nimg)
@@ -192,11 +208,20 @@ def parse_args(argv=None):
     p.add_argument('--image-snap', type=int, default=None, help='image grids every so many ticks (default: --snap; 0: none)')
     p.add_argument('--resume', help='a snapshot of this driver (.pt) or a reference network pickle (.pkl)')
     p.add_argument('--device', default='cuda')
+    p.add_argument('--metrics', default='none', help="'none' or a comma-separated list out of l1, psnr, ssim: reconstruction error of the snapshot "
+                   "grid's diagonal cells on image-snapshot ticks (the reference's fid50k_full etc. need a detector network and are refused)")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     a = parse_args(argv)
+    metrics = None
+    if a.metrics.strip().lower() not in ('', 'none'):
+        from . import metrics as metrics_mod
+        try:
+            metrics = metrics_mod.parse_metrics(a.metrics)
+        except ValueError as e:
+            raise SystemExit(str(e))
     return training_loop(a.outdir, a.data, batch=a.batch, batch_gpu=a.batch_gpu, gamma=a.gamma, l1_weight=a.l1_weight, mask_weight=a.mask_weight,
                          vgg_weight=a.vgg_weight, contextual_weight=a.contextual_weight, aug=a.aug, target=a.target, seed=a.seed, workers=a.workers,
-                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt)
+                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt, metrics=metrics)
