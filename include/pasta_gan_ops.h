@@ -11,7 +11,7 @@
  *                           16-bit: pg_conv2d16_{packed_size,pack_weight,pack_weight_grouped,forward,splitk_plan,forward_splitk,up2_fused,wgrad,wgrad_plan,wgrad_x3}, pg_adam_flat_{chunk,step},
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
- *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color
+ *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color, pg_augment_late
  *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8
  *   train_fetch_plugin.so   pg_train_fetch
  *   tryon_front_plugin.so   pg_tryon_front_stats, pg_tryon_front_bit_rows, pg_tryon_front_compose
@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 18
+#define PG_ABI_VERSION 19
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -654,6 +654,17 @@ int pg_augment_warp(const float* x, float* y, const float* g_inv, const int* mar
 int pg_augment_warp_adjoint(const float* dy, float* workspace, float* dx, const float* g_inv, const int* margins, const float* f,
                             int n, int c, int h, int w, void* stream);
 int pg_augment_color(const float* x, float* y, const float* mat, int n, int c, int hw, int mode, void* stream);
+/* pg_augment_late: the pipe's late stages (augment.py:372-431) in one launch.  F = the separable correlation with the per-sample 1-D filter `taps` (device
+ *   float32 [n, ntaps]; rows, then columns) behind a reflect pad of p = ntaps / 2 pixels; M = the cutout mask of `cut` (device float32 [n, 4] = centre x,
+ *   centre y, size x, size y, in units of the image: 0 where |(xi + 0.5) / w - cx| < sx / 2 and likewise in y, else 1; float32, true division);
+ *   `noise` = device [n, c, h, w], `sigma` = device [n].  A NULL `taps` / (`noise`, `sigma`) / `cut` switches that stage off.
+ *   mode 0 (affine): y = M (F x + noise sigma);  mode 1 (linear): y = M F x;  mode 2 (adjoint): y = F^T (M x).  Modes 1 and 2 ignore the noise.
+ *   The padded image and the row pass stay in LDS: no workspace.  No atomics: bit-identical per call.  Without a filter the noise is x + (noise sigma) with the
+ *   product rounded first (no fused multiply-add) and the mask multiplies by 0 or 1: torch's composition bit for bit.
+ *   PG_ERR_INVALID_ARG: NULL x / y, non-positive sizes, `noise` without `sigma` or the reverse, n * c > 65535, unknown mode.  PG_ERR_UNSUPPORTED: even
+ *   ntaps, ntaps > 43 (the kernel's tap registers and halo are built for Hz_fbank's 43), h <= p or w <= p (reflect padding needs p + 1 samples). */
+int pg_augment_late(const float* x, float* y, const float* taps, int ntaps, const float* noise, const float* sigma, const float* cut,
+                    int n, int c, int h, int w, int mode, void* stream);
 int pg_augment_abi_version(void);
 
 /* tryon_plugin.so -- the staging on either side of the generator in the try-on driver (training/tryon.py; reference test.py:126-181).  Results equal

@@ -237,6 +237,193 @@ __global__ void color_kernel(const float* __restrict__ x, float* __restrict__ y,
     }
 }
 
+// ---------------------------------------------------------------------------- late stages: imgfilter, noise, cutout (augment.py:372-431)
+//
+// One launch: a workgroup owns a kLateTH x kLateTW tile of one (sample, channel) plane.  It stages the tile with a kLateP-pixel halo in LDS (forward: the
+// reflect-padded source, gathered; adjoint: the masked gradient, zero outside the image), runs the row pass into a second LDS array (every staged row, tile
+// columns) and the column pass from there into registers; noise and cutout are the epilogue.  The padded image, the row-pass result and any workspace never
+// reach global memory.  A sample's taps are uniform over the workgroup: they are read once per thread at a uniform address (scalar registers), centred in
+// kLateTaps slots (zero beyond ntaps), so both passes unroll over compile-time tap indices; a copy in LDS serves the adjoint's edge terms.
+// Pitches (107, 65 dwords) are odd: the row pass walks lanes down a column of the staged tile, the column pass across a row of the row-pass result.
+//
+// Adjoint of the reflect-padded correlation, per axis (p = taps / 2; dy = 0 outside [0, H)):
+//     dx[i] = sum_k t[k] ( dy[i-k+p] + [1 <= i <= p] dy[-i-k+p] + [H-1-p <= i <= H-2] dy[2(H-1)-i-k+p] )
+// The first term is the forward pass with the taps reversed; the two mirror terms are evaluated only by the outputs next to an edge, and every source they
+// name lies in [i-p, i+p] clipped to the image, i.e. inside the staged halo.  A gather: no atomics, bit-identical per call.
+
+constexpr int kLateTaps = 43;                 // Hz_fbank.shape[1]: the largest filter the kernel is built for
+constexpr int kLateP = kLateTaps / 2;         // 21
+constexpr int kLateTH = 32, kLateTW = 64;     // output tile
+constexpr int kLateSH = kLateTH + 2 * kLateP; // 74 staged rows
+constexpr int kLateSW = kLateTW + 2 * kLateP; // 106 staged columns
+constexpr int kLateSPitch = kLateSW + 1;      // 107
+constexpr int kLateMPitch = kLateTW + 1;      // 65
+constexpr int kLateR = 8;                     // outputs per thread and pass (a sliding window of kLateR + 2 kLateP inputs)
+constexpr int kLateThreads = 256;
+
+// cutout mask of one pixel in the reference's float32 arithmetic (augment.py:427-430): 1 outside the box, 0 inside
+__device__ inline float late_mask(const float* cut, int xi, int yi, int h, int w) {
+#pragma clang fp contract(off)
+    const bool mx = fabsf(((float)xi + 0.5f) / (float)w - cut[0]) >= cut[2] / 2.0f;
+    const bool my = fabsf(((float)yi + 0.5f) / (float)h - cut[1]) >= cut[3] / 2.0f;
+    return (mx || my) ? 1.0f : 0.0f;
+}
+
+// v -> M (v + noise sigma): the product is rounded before the sum (torch's `images + randn * sigma`), the mask multiplies by 0 or 1
+__device__ inline float late_epilogue(float v, const float* noise, int64_t at, float sigma, const float* cut, int xi, int yi, int h, int w) {
+#pragma clang fp contract(off)
+    if (noise) {
+        const float t = noise[at] * sigma;
+        v = v + t;
+    }
+    if (cut) v = v * late_mask(cut, xi, yi, h, w);
+    return v;
+}
+
+// without a filter: mode 0: y = M (x + noise sigma); modes 1, 2: y = M x.  One thread = kVec consecutive pixels of a row (kVec = 4: 16-byte loads and
+// stores, taken when w % 4 == 0 and the pointers are 16-byte aligned; else 1); `noise` / `sigma` arrive null where the mode ignores them.
+template <int kVec>
+__global__ void late_pointwise(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ noise, const float* __restrict__ sigma,
+                               const float* __restrict__ cut, int C, int h, int w) {
+    typedef pg::vec_t<float, kVec> vec;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= h * w / kVec) return;
+    const int n = blockIdx.y / C, pix = q * kVec;
+    const int64_t at = (int64_t)blockIdx.y * h * w + pix;
+    const int xi = pix % w, yi = pix / w;
+    const float* cutn = cut ? cut + 4 * n : nullptr;
+    const float sg = noise ? sigma[n] : 0.0f;
+    vec v = *reinterpret_cast<const vec*>(x + at), nz;
+    if (noise) nz = *reinterpret_cast<const vec*>(noise + at);
+#pragma unroll
+    for (int k = 0; k < kVec; k++) {
+#pragma clang fp contract(off)
+        float r = v.v[k];
+        if (noise) {
+            const float t = nz.v[k] * sg;
+            r = r + t;
+        }
+        if (cutn) r = r * late_mask(cutn, xi + k, yi, h, w);
+        v.v[k] = r;
+    }
+    *reinterpret_cast<vec*>(y + at) = v;
+}
+
+// One mirror term of the adjoint along an axis of length `n`: sum_k T[k] src[idx(k)], idx(k) = base - k, over the k whose idx lies in the image and in the
+// staged range [origin, origin + staged) (`src` = staged element 0, `stride` dwords apart).  A rolled loop: only the outputs next to an edge come here.
+__device__ inline float late_mirror(const float* T, const float* src, int stride, int base, int n, int origin, int staged) {
+    const int klo = max(0, base - min(n, origin + staged) + 1), khi = min(kLateTaps - 1, base - max(0, origin));
+    float s = 0.0f;
+#pragma unroll 1
+    for (int k = klo; k <= khi; k++) s += T[k] * src[(base - k - origin) * stride];
+    return s;
+}
+
+template <bool kAdj>
+__global__ __launch_bounds__(kLateThreads) void late_filter(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ taps, int ntaps,
+                                                            const float* __restrict__ noise, const float* __restrict__ sigma,
+                                                            const float* __restrict__ cut, int C, int h, int w, int tiles_x) {
+    __shared__ float S[kLateSH * kLateSPitch];
+    __shared__ float Mid[kLateSH * kLateMPitch];
+    __shared__ float T[kLateTaps];
+    const int tid = threadIdx.x;
+    const int n = blockIdx.y / C;
+    const int x0 = (blockIdx.x % tiles_x) * kLateTW, y0 = (blockIdx.x / tiles_x) * kLateTH;
+    const int p = ntaps / 2, shift = kLateP - p;
+    const float* plane = x + (int64_t)blockIdx.y * h * w;
+    const float* cutn = cut ? cut + 4 * n : nullptr;
+
+    // taps, centred in kLateTaps slots; the adjoint's main term runs the forward loop with the taps reversed
+    float t[kLateTaps];
+#pragma unroll
+    for (int k = 0; k < kLateTaps; k++) {
+        const int q = (kAdj ? kLateTaps - 1 - k : k) - shift;
+        t[k] = (q >= 0 && q < ntaps) ? taps[n * ntaps + q] : 0.0f;
+    }
+    if (tid < kLateTaps) {
+        const int q = tid - shift;
+        T[tid] = (q >= 0 && q < ntaps) ? taps[n * ntaps + q] : 0.0f;      // unreversed, for the mirror terms
+    }
+
+    // stage the tile and its halo
+    for (int e = tid; e < kLateSH * kLateSW; e += kLateThreads) {
+        const int r = e / kLateSW, c = e % kLateSW;
+        const int gy = y0 - kLateP + r, gx = x0 - kLateP + c;
+        float v = 0.0f;
+        if (kAdj) {
+            if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
+                v = plane[(int64_t)gy * w + gx];
+                if (cutn) v = v * late_mask(cutn, gx, gy, h, w);
+            }
+        } else if (gy >= -p && gy < h + p && gx >= -p && gx < w + p) {   // further out only zero taps look: keep 0 x inf out of the sums
+            v = plane[(int64_t)reflect(gy, h) * w + reflect(gx, w)];
+        }
+        S[r * kLateSPitch + c] = v;
+    }
+    __syncthreads();
+
+    // row pass: every staged row, tile columns; one thread = kLateR consecutive columns of one row, lanes down the rows
+    for (int task = tid; task < kLateSH * (kLateTW / kLateR); task += kLateThreads) {
+        const int r = task % kLateSH, c0 = (task / kLateSH) * kLateR;
+        const float* row = S + r * kLateSPitch;
+        float acc[kLateR];
+#pragma unroll
+        for (int j = 0; j < kLateR; j++) acc[j] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < kLateR + 2 * kLateP; i++) {
+            const float v = row[c0 + i];
+#pragma unroll
+            for (int j = 0; j < kLateR; j++)
+                if (i - j >= 0 && i - j < kLateTaps) acc[j] += t[i - j] * v;
+        }
+        if (kAdj) {
+#pragma unroll
+            for (int j = 0; j < kLateR; j++) {
+                const int gx = x0 + c0 + j;
+                if (gx >= w) continue;
+                if (gx >= 1 && gx <= kLateP) acc[j] += late_mirror(T, row, 1, kLateP - gx, w, x0 - kLateP, kLateSW);
+                if (gx >= w - 1 - kLateP && gx <= w - 2) acc[j] += late_mirror(T, row, 1, 2 * (w - 1) - gx + kLateP, w, x0 - kLateP, kLateSW);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kLateR; j++) Mid[r * kLateMPitch + c0 + j] = acc[j];
+    }
+    __syncthreads();
+
+    // column pass: one thread = kLateR consecutive rows of one column, lanes across the columns
+    {
+        const int c = tid % kLateTW, r0 = (tid / kLateTW) * kLateR;
+        const float* col = Mid + c;
+        float acc[kLateR];
+#pragma unroll
+        for (int j = 0; j < kLateR; j++) acc[j] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < kLateR + 2 * kLateP; i++) {
+            const float v = col[(r0 + i) * kLateMPitch];
+#pragma unroll
+            for (int j = 0; j < kLateR; j++)
+                if (i - j >= 0 && i - j < kLateTaps) acc[j] += t[i - j] * v;
+        }
+        const int gx = x0 + c;
+        if (gx >= w) return;
+        const float sg = (!kAdj && noise) ? sigma[n] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < kLateR; j++) {
+            const int gy = y0 + r0 + j;
+            if (gy >= h) continue;
+            float v = acc[j];
+            if (kAdj) {
+                if (gy >= 1 && gy <= kLateP) v += late_mirror(T, col, kLateMPitch, kLateP - gy, h, y0 - kLateP, kLateSH);
+                if (gy >= h - 1 - kLateP && gy <= h - 2) v += late_mirror(T, col, kLateMPitch, 2 * (h - 1) - gy + kLateP, h, y0 - kLateP, kLateSH);
+            } else {
+                const int64_t at = ((int64_t)blockIdx.y * h + gy) * w + gx;
+                v = late_epilogue(v, noise, at, sg, cutn, gx, gy, h, w);
+            }
+            y[((int64_t)blockIdx.y * h + gy) * w + gx] = v;
+        }
+    }
+}
+
 bool warp_args_ok(int n, int c, int h, int w) {
     return n > 0 && c > 0 && h >= 2 && w >= 2 && n <= 65535 && (int64_t)n * ((c + kCh - 1) / kCh) <= 65535 && (int64_t)n * c <= 65535;
 }
@@ -279,5 +466,33 @@ PG_EXPORT int pg_augment_color(const float* x, float* y, const float* mat, int n
     const dim3 grid((hw + 255) / 256, n);
     if (c == 3) hipLaunchKernelGGL(color_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, x, y, mat, hw, mode);
     else hipLaunchKernelGGL(color_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, y, mat, hw, mode);
+    return pg::launch_status();
+}
+
+PG_EXPORT int pg_augment_late(const float* x, float* y, const float* taps, int ntaps, const float* noise, const float* sigma, const float* cut,
+                              int n, int c, int h, int w, int mode, void* stream) {
+    if (!x || !y || n <= 0 || c <= 0 || h <= 0 || w <= 0 || mode < 0 || mode > 2 || (noise == nullptr) != (sigma == nullptr)) return PG_ERR_INVALID_ARG;
+    if ((int64_t)n * c > 65535) return PG_ERR_INVALID_ARG;
+    if ((int64_t)h * w >= 0x7fffffffLL) return PG_ERR_TOO_LARGE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!taps) {
+        const float* nz = mode == 0 ? noise : nullptr;
+        const float* sg = mode == 0 ? sigma : nullptr;
+        if (w % 4 == 0 && pg::aligned16(x) && pg::aligned16(y) && (!nz || pg::aligned16(nz)))
+            hipLaunchKernelGGL(late_pointwise<4>, dim3((h * w / 4 + 255) / 256, n * c), dim3(256), 0, s, x, y, nz, sg, cut, c, h, w);
+        else
+            hipLaunchKernelGGL(late_pointwise<1>, dim3((h * w + 255) / 256, n * c), dim3(256), 0, s, x, y, nz, sg, cut, c, h, w);
+        return pg::launch_status();
+    }
+    if (ntaps <= 0) return PG_ERR_INVALID_ARG;
+    if (ntaps % 2 == 0 || ntaps > kLateTaps || h <= ntaps / 2 || w <= ntaps / 2) return PG_ERR_UNSUPPORTED;
+    const int tiles_x = (w + kLateTW - 1) / kLateTW, tiles_y = (h + kLateTH - 1) / kLateTH;
+    if ((int64_t)tiles_x * tiles_y > 0x7fffffffLL) return PG_ERR_TOO_LARGE;
+    const dim3 grid(tiles_x * tiles_y, n * c);
+    if (mode == 2)
+        hipLaunchKernelGGL(late_filter<true>, grid, dim3(kLateThreads), 0, s, x, y, taps, ntaps, nullptr, nullptr, cut, c, h, w, tiles_x);
+    else
+        hipLaunchKernelGGL(late_filter<false>, grid, dim3(kLateThreads), 0, s, x, y, taps, ntaps, mode == 0 ? noise : nullptr, mode == 0 ? sigma : nullptr,
+                           cut, c, h, w, tiles_x);
     return pg::launch_status();
 }

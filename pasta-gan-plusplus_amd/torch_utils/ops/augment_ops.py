@@ -1,9 +1,11 @@
-"""The two image operators of ADA's AugmentPipe (training/augment.py), on MI355X.
+"""The image operators of ADA's AugmentPipe (training/augment.py), on MI355X.
 
 ``geometric(x, g_inv, margins, f)`` is the reference's "Execute geometric transformations" block (augment.py:270-301): reflect-pad
 by the per-sample-derived margin, 2x upsample with the sym6 filter `f`, per-sample affine bilinear resampling, 2x downsample.
-``color(x, C)`` is its "Execute color transformations" block (augment.py:356-366).  Both are linear in the image; the sampling
-matrices, margins and colour matrices carry no gradient (AugmentPipe is ``requires_grad_(False)``).
+``color(x, C)`` is its "Execute color transformations" block (augment.py:356-366).  ``late(x, taps, noise, sigma, cut)`` is the rest
+of the pipe (augment.py:372-431): the per-sample separable image filter behind its reflect pad, additive noise and cutout, one
+``pg_augment_late`` launch.  All are affine in the image; the sampling matrices, margins, colour matrices and late parameters carry
+no gradient (AugmentPipe is ``requires_grad_(False)``).
 
 Dispatch follows the other ops: a GPU tensor runs ``csrc/augment.hip`` (``pg_augment_warp`` / ``pg_augment_warp_adjoint`` /
 ``pg_augment_color``) with the downsample on ``pg_upfirdn2d``, and never reads a value to the host; a CPU tensor runs the
@@ -31,8 +33,10 @@ def _init():
         plugin.lib.pg_augment_warp.argtypes = [p, p, p, p, p, i, i, i, i, p]
         plugin.lib.pg_augment_warp_adjoint.argtypes = [p, p, p, p, p, p, i, i, i, i, p]
         plugin.lib.pg_augment_color.argtypes = [p, p, p, i, i, i, i, p]
-        for fn in (plugin.lib.pg_augment_warp, plugin.lib.pg_augment_warp_adjoint, plugin.lib.pg_augment_color):
+        plugin.lib.pg_augment_late.argtypes = [p, p, p, i, p, p, p, i, i, i, i, i, p]
+        for fn in (plugin.lib.pg_augment_warp, plugin.lib.pg_augment_warp_adjoint, plugin.lib.pg_augment_color, plugin.lib.pg_augment_late):
             fn.restype = ctypes.c_int
+        plugin.late = plugin.lib.pg_augment_late          # bound once: the late stages' host path is as long as their kernels
         _plugin = plugin
     return True
 
@@ -134,6 +138,63 @@ class _Color(torch.autograd.Function):
         return _Color.apply(dy.contiguous(), mat, _COLOR_LINEAR if ctx.mode == _COLOR_TRANSPOSE else _COLOR_TRANSPOSE), None, None
 
 
+_LATE_AFFINE, _LATE_LINEAR, _LATE_ADJOINT = 0, 1, 2           # pg_augment_late modes
+MAX_LATE_TAPS = 43      # Hz_fbank.shape[1]: what csrc/augment.hip is built for
+
+
+_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
+
+
+def _late_native(x, taps, noise, sigma, cut, mode):
+    """One pg_augment_late launch on checked, contiguous tensors (a None: that stage is off).  These stages are short next to their host work, so the
+    call is kept lean: raw addresses, and no device guard where the image's device is already current."""
+    if _plugin is None:
+        _init()
+    n, c, h, w = x.shape
+    y = torch.empty_like(x)
+    index = x.device.index
+    guard = None
+    if index != torch.cuda.current_device():
+        guard = torch.cuda.device(index)
+        guard.__enter__()
+    try:
+        stream = _raw_stream(index) if _raw_stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        st = _plugin.late(x.data_ptr(), y.data_ptr(), taps.data_ptr() if taps is not None else None, taps.shape[1] if taps is not None else 0,
+                          noise.data_ptr() if noise is not None else None, sigma.data_ptr() if sigma is not None else None,
+                          cut.data_ptr() if cut is not None else None, n, c, h, w, mode, stream)
+    finally:
+        if guard is not None:
+            guard.__exit__(None, None, None)
+    if st != 0:
+        nat.check(st, 'pg_augment_late')
+    return y
+
+
+class _Late(torch.autograd.Function):
+    """mode AFFINE: y = M (F x + noise sigma); LINEAR: y = M F x; ADJOINT: y = F^T (M x) (F = the reflect-padded separable filter, M = the cutout mask).
+    Backward: AFFINE and LINEAR -> ADJOINT, ADJOINT -> LINEAR (the noise drops out of every derivative; with neither F nor M it is the identity)."""
+    @staticmethod
+    def forward(ctx, x, taps, noise, sigma, cut, mode):
+        ctx.params = (taps, cut)
+        ctx.mode = mode
+        return _late_native(x, taps, noise, sigma, cut, mode)
+
+    @staticmethod
+    def backward(ctx, dy):
+        taps, cut = ctx.params
+        if taps is None and cut is None:
+            return dy, None, None, None, None, None
+        mode = _LATE_LINEAR if ctx.mode == _LATE_ADJOINT else _LATE_ADJOINT
+        return _late_apply(dy.contiguous(), taps, None, None, cut, mode), None, None, None, None, None
+
+
+def _late_apply(x, taps, noise, sigma, cut, mode):
+    """Through autograd only where a gradient is being recorded."""
+    if x.requires_grad and torch.is_grad_enabled():
+        return _Late.apply(x, taps, noise, sigma, cut, mode)
+    return _late_native(x, taps, noise, sigma, cut, mode)
+
+
 # ---------------------------------------------------------------------------- public ops
 
 def _translate2d(tx, ty, like):
@@ -229,3 +290,74 @@ def color(x, C):
         Cm = C[:, :3, :].mean(dim=1, keepdims=True)
         mat = torch.cat([Cm[:, :, :3].sum(dim=2, keepdims=True), Cm[:, :, 3:]], dim=2).contiguous()
     return _Color.apply(x, mat, _COLOR_AFFINE)
+
+
+
+def late_reference(x, taps, noise, sigma, cut):
+    """The reference composition (augment.py:397-431) in plain torch, in the image's dtype."""
+    n, c, h, w = x.shape
+    if taps is not None:
+        f = taps.to(x.dtype).unsqueeze(1).repeat([1, c, 1]).reshape([n * c, 1, -1])
+        p = taps.shape[1] // 2
+        x = x.reshape([1, n * c, h, w])
+        x = torch.nn.functional.pad(input=x, pad=[p, p, p, p], mode='reflect')
+        x = torch.nn.functional.conv2d(x, f.unsqueeze(2), groups=n * c)
+        x = torch.nn.functional.conv2d(x, f.unsqueeze(3), groups=n * c)
+        x = x.reshape([n, c, h, w])
+    if noise is not None:
+        x = x + noise.to(x.dtype) * sigma.to(x.dtype).reshape([n, 1, 1, 1])
+    if cut is not None:
+        cut = cut.to(x.dtype)
+        center, size = cut[:, :2].reshape([n, 2, 1, 1, 1]), cut[:, 2:].reshape([n, 2, 1, 1, 1])
+        coord_x = torch.arange(w, device=x.device).reshape([1, 1, 1, -1])
+        coord_y = torch.arange(h, device=x.device).reshape([1, 1, -1, 1])
+        mask_x = (((coord_x + 0.5) / w - center[:, 0]).abs() >= size[:, 0] / 2)
+        mask_y = (((coord_y + 0.5) / h - center[:, 1]).abs() >= size[:, 1] / 2)
+        x = x * torch.logical_or(mask_x, mask_y).to(x.dtype)
+    return x
+
+
+def _check_late(x, taps, noise, sigma, cut):
+    n, c, h, w = x.shape
+    dev, f32, T = x.device, torch.float32, torch.Tensor
+    if taps is not None:
+        if not (isinstance(taps, T) and taps.ndim == 2 and taps.dtype == f32 and taps.shape[0] == n and taps.device == dev):
+            raise nat.NativeOpError('augment late: taps must be float32 [N, K] on the images\' device')
+        k = taps.shape[1]
+        if k % 2 == 0 or k > MAX_LATE_TAPS:
+            raise nat.NativeOpError(f'augment late: the filter must have an odd number of taps, at most {MAX_LATE_TAPS}; got {k}')
+        if h <= k // 2 or w <= k // 2:
+            raise nat.NativeOpError(f'augment late: reflect padding by {k // 2} needs H, W >= {k // 2 + 1}')
+        if taps.requires_grad or not taps.is_contiguous():
+            taps = taps.detach().contiguous()
+    if (noise is None) != (sigma is None):
+        raise nat.NativeOpError('augment late: noise and sigma come together')
+    if noise is not None:
+        if not (isinstance(noise, T) and isinstance(sigma, T) and noise.dtype == f32 and sigma.dtype == f32 and noise.shape == x.shape
+                and sigma.numel() == n and noise.device == dev and sigma.device == dev):
+            raise nat.NativeOpError('augment late: noise must be float32 [N, C, H, W] and sigma float32 [N] on the images\' device')
+        if noise.requires_grad or not noise.is_contiguous():
+            noise = noise.detach().contiguous()
+        if sigma.requires_grad or not sigma.is_contiguous():
+            sigma = sigma.detach().contiguous()
+    if cut is not None:
+        if not (isinstance(cut, T) and cut.dtype == f32 and cut.shape == (n, 4) and cut.device == dev):
+            raise nat.NativeOpError('augment late: cut must be float32 [N, 4] (centre x, centre y, size x, size y) on the images\' device')
+        if cut.requires_grad or not cut.is_contiguous():
+            cut = cut.detach().contiguous()
+    return taps, noise, sigma, cut
+
+
+def late(x, taps=None, noise=None, sigma=None, cut=None):
+    """AugmentPipe's late stages in the reference's order: `taps` = per-sample 1-D filters [N, K] (K odd; rows, then columns, behind a reflect pad of
+    K // 2), `noise` [N, C, H, W] scaled by `sigma` [N] and added, `cut` = [N, 4] (centre x, centre y, size x, size y in units of the image) zeroed.
+    None switches a stage off.  Output has the input's shape; the parameters carry no gradient."""
+    assert isinstance(x, torch.Tensor)
+    if taps is None and noise is None and sigma is None and cut is None:
+        return x
+    if x.device.type != 'cuda':
+        det = lambda t: None if t is None else t.detach()
+        return late_reference(x, det(taps), det(noise), det(sigma), det(cut))
+    x = _check_image(x, 'augment late')
+    taps, noise, sigma, cut = _check_late(x, taps, noise, sigma, cut)
+    return _late_apply(x, taps, noise, sigma, cut, _LATE_AFFINE)

@@ -6,8 +6,10 @@ snapshot's ``augment_pipe`` loads with ``checkpoint.load_into(pipe, snapshot, ke
 ``torch.rand`` / ``torch.randn`` calls, so that on one device and seed the same augmentation is drawn.  ``forward`` is split into
 ``sample_params`` (plain torch on [N, 3, 3] / [N, 4, 4] matrices; nothing is read to the host -- the margins are clamped and
 ceiled on the device) and ``apply``, whose geometric and colour blocks are ``torch_utils.ops.augment_ops`` (HIP kernels on a GPU
-tensor, the reference composition on a CPU tensor).  ``imgfilter`` has no native kernel: on a GPU tensor it raises
-NotImplementedError (the default ``bgc`` pipe and ``train.sh`` never enable it).
+tensor, the reference composition on a CPU tensor).  The late stages (``imgfilter``, ``noise``, ``cutout``) are split the same way
+into ``sample_late`` and ``apply_late``; ``set_native_late(True)`` (the training driver does it) runs them on a GPU tensor as one
+``pg_augment_late`` launch.  Without that switch a GPU tensor takes the torch composition, and ``imgfilter`` raises
+NotImplementedError there.
 """
 
 import itertools
@@ -171,6 +173,8 @@ class AugmentPipe(torch.nn.Module):
         # image-space corruptions
         self.noise, self.cutout, self.noise_std, self.cutout_size = float(noise), float(cutout), float(noise_std), float(cutout_size)
 
+        self.native_late = False                         # set_native_late(): a plain attribute, not a buffer
+
         sym6 = torch.as_tensor(daubechies_symlet(6), dtype=torch.float32)
         self.register_buffer('Hz_geom', sym6 / sym6.sum())  # upfirdn2d.setup_filter(sym6): 12 taps -> separable, normalised
         self.register_buffer('Hz_fbank', torch.as_tensor(_filter_bank(daubechies2()), dtype=torch.float32))
@@ -296,23 +300,37 @@ class AugmentPipe(torch.nn.Module):
         return G_inv, margins, C
 
     def apply(self, images, params, debug_percentile=None):
-        """Run a drawn augmentation (`params` from sample_params) on `images`; the later stages (imgfilter, noise, cutout) draw here,
-        in the reference's order."""
+        """Run a drawn augmentation (`params` from sample_params) on `images`; the later stages (imgfilter, noise, cutout) are drawn here
+        (sample_late), in the reference's order, and run by apply_late."""
         assert isinstance(images, torch.Tensor) and images.ndim == 4
         batch_size, num_channels, height, width = images.shape
         device = images.device
         G_inv, margins, C = params
-        if debug_percentile is not None:
-            debug_percentile = torch.as_tensor(debug_percentile, dtype=torch.float32, device=device)
         if G_inv is not None:
             images = augment_ops.geometric(images, G_inv, margins, self.Hz_geom)
         if C is not None:
             images = augment_ops.color(images, C)
 
-        if self.imgfilter > 0:   # augment.py:372-404
-            if images.device.type == 'cuda':
-                raise NotImplementedError('AugmentPipe: the imgfilter stage has no native kernel (its grouped depthwise convolution); '
-                                          'use a pipe without imgfilter (e.g. "bgc") on the GPU')
+        if self.imgfilter > 0 and images.device.type == 'cuda' and not self.native_late:
+            raise NotImplementedError('AugmentPipe: the imgfilter stage runs on the GPU only on the native route (set_native_late(True)); '
+                                      'without it use a pipe without imgfilter (e.g. "bgc") on the GPU')
+        late = self.sample_late(batch_size, num_channels, height, width, device, debug_percentile=debug_percentile)
+        return self.apply_late(images, late)
+
+    def set_native_late(self, native=True):
+        """Run the late stages (imgfilter, noise, cutout) of a GPU tensor as one ``pg_augment_late`` launch instead of the torch composition (which has no
+        imgfilter on the GPU).  A plain attribute, not a buffer: ``state_dict()`` is unchanged.  CPU tensors are unaffected.  Returns self."""
+        self.native_late = bool(native)
+        return self
+
+    def sample_late(self, batch_size, num_channels, height, width, device, debug_percentile=None):
+        """Draw the late stages in the reference's order (augment.py:372-431): per band randn then rand; the noise's randn, rand and the [N, C, H, W]
+        randn; the cutout's rand, rand.  Returns (taps [N, K] or None, noise [N, C, H, W] or None, sigma [N] or None, cut [N, 4] = centre x, centre y,
+        size x, size y, or None); None = the stage is off.  Nothing is read to the host."""
+        if debug_percentile is not None:
+            debug_percentile = torch.as_tensor(debug_percentile, dtype=torch.float32, device=device)
+        taps = noise = sigma = cut = None
+        if self.imgfilter > 0:   # augment.py:372-395
             num_bands = self.Hz_fbank.shape[0]
             assert len(self.imgfilter_bands) == num_bands
             expected_power = _constant(np.array([10, 1, 1, 1]) / 13, device)
@@ -326,34 +344,33 @@ class AugmentPipe(torch.nn.Module):
                 t[:, i] = t_i
                 t = t / (expected_power * t.square()).sum(dim=-1, keepdims=True).sqrt()
                 g = g * t
-            Hz_prime = (g @ self.Hz_fbank).unsqueeze(1).repeat([1, num_channels, 1]).reshape([batch_size * num_channels, 1, -1])
-            p = self.Hz_fbank.shape[1] // 2
-            images = images.reshape([1, batch_size * num_channels, height, width])
-            images = torch.nn.functional.pad(input=images, pad=[p, p, p, p], mode='reflect')
-            images = torch.nn.functional.conv2d(images, Hz_prime.unsqueeze(2).to(images.dtype), groups=batch_size * num_channels)
-            images = torch.nn.functional.conv2d(images, Hz_prime.unsqueeze(3).to(images.dtype), groups=batch_size * num_channels)
-            images = images.reshape([batch_size, num_channels, height, width])
+            taps = g @ self.Hz_fbank
 
         if self.noise > 0:   # augment.py:410-416
             sigma = torch.randn([batch_size, 1, 1, 1], device=device).abs() * self.noise_std
             sigma = torch.where(torch.rand([batch_size, 1, 1, 1], device=device) < self.noise * self.p, sigma, torch.zeros_like(sigma))
             if debug_percentile is not None:
                 sigma = torch.full_like(sigma, torch.erfinv(debug_percentile) * self.noise_std)
-            images = images + torch.randn([batch_size, num_channels, height, width], device=device) * sigma
+            sigma = sigma.reshape([batch_size])
+            noise = torch.randn([batch_size, num_channels, height, width], device=device)
 
-        if self.cutout > 0:  # augment.py:419-431
+        if self.cutout > 0:  # augment.py:419-426
             size = torch.full([batch_size, 2, 1, 1, 1], self.cutout_size, device=device)
             size = torch.where(torch.rand([batch_size, 1, 1, 1, 1], device=device) < self.cutout * self.p, size, torch.zeros_like(size))
             center = torch.rand([batch_size, 2, 1, 1, 1], device=device)
             if debug_percentile is not None:
                 size = torch.full_like(size, self.cutout_size)
                 center = torch.full_like(center, debug_percentile)
-            coord_x = torch.arange(width, device=device).reshape([1, 1, 1, -1])
-            coord_y = torch.arange(height, device=device).reshape([1, 1, -1, 1])
-            mask_x = (((coord_x + 0.5) / width - center[:, 0]).abs() >= size[:, 0] / 2)
-            mask_y = (((coord_y + 0.5) / height - center[:, 1]).abs() >= size[:, 1] / 2)
-            images = images * torch.logical_or(mask_x, mask_y).to(images.dtype)
-        return images
+            cut = torch.cat([center.reshape([batch_size, 2]), size.reshape([batch_size, 2])], dim=1)
+        return taps, noise, sigma, cut
+
+    def apply_late(self, images, late):
+        """Run drawn late stages (`late` from sample_late): the filter behind its reflect pad (augment.py:397-404), then the noise, then the cutout.
+        A GPU tensor takes ``pg_augment_late`` when ``native_late`` is set, else the torch composition; a CPU tensor always the composition."""
+        taps, noise, sigma, cut = late
+        if images.device.type == 'cuda' and not self.native_late:
+            return augment_ops.late_reference(images, taps, noise, sigma, cut)
+        return augment_ops.late(images, taps, noise, sigma, cut)
 
     def forward(self, images, debug_percentile=None):
         assert isinstance(images, torch.Tensor) and images.ndim == 4

@@ -79,15 +79,34 @@ def image_interval(snap, image_snap):
     return (snap if image_snap is None else image_snap) or 0
 
 
+def check_augment_options(aug, p, augpipe):
+    """The option rules of the reference's train.py (:259-296); ValueError with the text the command line prints."""
+    if aug not in ('ada', 'noaug', 'fixed'):
+        raise ValueError("--aug must be 'ada', 'noaug' or 'fixed'")
+    if aug == 'fixed' and p is None:
+        raise ValueError('--aug=fixed requires specifying --p')
+    if p is not None:
+        if aug != 'fixed':
+            raise ValueError('--p can only be specified with --aug=fixed')
+        if not 0 <= p <= 1:
+            raise ValueError('--p must be between 0 and 1')
+    if augpipe not in augment.AUGPIPE_SPECS:
+        raise ValueError(f'--augpipe must be one of {", ".join(augment.AUGPIPE_SPECS)}')
+    if augpipe != 'bgc' and aug == 'noaug':
+        raise ValueError('--augpipe cannot be specified with --aug=noaug')
+
+
 def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, mask_weight=1.0, vgg_weight=0, contextual_weight=0, aug='ada', target=0.6,
                   seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None,
-                  vgg_ckpt=None, metrics=None):
+                  vgg_ckpt=None, metrics=None, augpipe='bgc', p=None):
     """Train on the dataset directory `data` for `kimg` thousand images (one process, one GPU: `batch` = `batch_gpu` x accumulation rounds).
     Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied.
     `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none).
     `vgg_weight` > 0 turns the VGG19 perceptual term on and needs `vgg_ckpt` (no default path): NotImplementedError without one, FileNotFoundError for
     a path that does not exist, both before any network is built.  `metrics`: None, or names out of 'l1', 'psnr', 'ssim' -- each image-snapshot tick
-    then adds ``Metric/recon_<name>`` (training/metrics.py) to its ``stats.jsonl`` line and prints them after the status line."""
+    then adds ``Metric/recon_<name>`` (training/metrics.py) to its ``stats.jsonl`` line and prints them after the status line.
+    `aug`: 'ada' (adaptive, towards `target`), 'fixed' (the constant probability `p`, which also wins over a resumed snapshot's) or 'noaug'; `augpipe` names
+    the pipeline out of ``augment.AUGPIPE_SPECS`` (reference train.py:259-305).  On a GPU the pipe's late stages run natively (``set_native_late``)."""
     if vgg_weight and vgg_ckpt is None:
         raise NotImplementedError('vgg_weight > 0 needs --vgg_ckpt: a torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth is not shipped)')
     if vgg_weight and not os.path.isfile(vgg_ckpt):
@@ -98,8 +117,7 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
         metrics = metrics_mod.parse_metrics(metrics)
     if batch % batch_gpu:
         raise ValueError('--batch must be a multiple of --batch-gpu')
-    if aug not in ('ada', 'noaug'):
-        raise ValueError("--aug must be 'ada' or 'noaug'")
+    check_augment_options(aug, p, augpipe)
     dev = torch.device(device)
     os.makedirs(run_dir, exist_ok=True)
     torch.manual_seed(seed)
@@ -125,7 +143,9 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
         vgg = vgg_loss.VGGLoss(vgg_loss.VGG19Features(vgg_loss.load_vgg19(vgg_ckpt))).to(dev)
     loss = StyleGAN2Loss(device=dev, **parts, D=D, D_parsing=D_parsing, style_mixing_prob=0.9, r1_gamma=gamma, l1_weight=l1_weight, vgg_weight=vgg_weight,
                          vgg=vgg, contextual_weight=contextual_weight, mask_weight=mask_weight, report=report)
-    pipe = augment.AugmentPipe(**augment.AUGPIPE_SPECS['bgc']).to(dev) if aug == 'ada' else None
+    pipe = augment.AugmentPipe(**augment.AUGPIPE_SPECS[augpipe]).to(dev).set_native_late(dev.type == 'cuda') if aug != 'noaug' else None
+    if aug == 'fixed':
+        augment_p = p
     step = TrainingStep(parts, D, D_parsing, loss, batch_size=batch, G_ema_parts=g_parts(G_ema), augment_pipe=pipe,
                         augment_p=augment_p if augment_p is not None else 0, ada_target=target if aug == 'ada' else None)
     step.cur_nimg = start_nimg
@@ -198,8 +218,10 @@ def parse_args(argv=None):
     p.add_argument('--vgg_weight', type=float, default=0, help='weight of the VGG19 perceptual term (the reference\'s train.sh: 20); > 0 needs --vgg_ckpt')
     p.add_argument('--vgg_ckpt', default=None, help='torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth); no default path')
     p.add_argument('--contextual_weight', type=float, default=0, help='only 0 is supported')
-    p.add_argument('--aug', choices=['ada', 'noaug'], default='ada')
+    p.add_argument('--aug', choices=['ada', 'noaug', 'fixed'], default='ada', help="augmentation mode; 'fixed' needs --p")
+    p.add_argument('--p', type=float, default=None, help='augmentation probability for --aug=fixed')
     p.add_argument('--target', type=float, default=0.6, help='ADA target')
+    p.add_argument('--augpipe', choices=list(augment.AUGPIPE_SPECS), default='bgc', help='augmentation pipeline')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--workers', type=int, default=3, help='DataLoader worker processes')
     p.add_argument('--kimg', type=float, default=25000, help='training length in thousands of images')
@@ -222,6 +244,11 @@ def main(argv=None):
             metrics = metrics_mod.parse_metrics(a.metrics)
         except ValueError as e:
             raise SystemExit(str(e))
+    try:
+        check_augment_options(a.aug, a.p, a.augpipe)
+    except ValueError as e:
+        raise SystemExit(str(e))
     return training_loop(a.outdir, a.data, batch=a.batch, batch_gpu=a.batch_gpu, gamma=a.gamma, l1_weight=a.l1_weight, mask_weight=a.mask_weight,
                          vgg_weight=a.vgg_weight, contextual_weight=a.contextual_weight, aug=a.aug, target=a.target, seed=a.seed, workers=a.workers,
-                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt, metrics=metrics)
+                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt, metrics=metrics,
+                         augpipe=a.augpipe, p=a.p)
