@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 19
+#define PG_ABI_VERSION 20
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -327,6 +327,23 @@ int64_t pg_conv2d_stem7x3_packed_size(int Cout);
 int pg_conv2d_stem7x3_pack_weight(const float* w, void* packed, int Cout, float scale, int flip_hw, void* stream);
 int pg_conv2d_stem7x3_forward(const float* x, const void* packed, float* y, int N, int H, int W, int Cout, const int64_t ystride[4],
                               const pg_conv2d_fusion* fusion, void* stream);
+
+/* ABI 20 -- the fp32 stride-2 3x3 convolution with padding 0 (what follows the FIR pass of a `down = 2` 3x3 layer: conv2d_resample.py:119-122 ->
+ * conv2d_gradfix.conv2d, bias_act in the epilogue, networks.py:170-179) on the bf16 matrix pipe (csrc/conv2d_s2x3.h): x [N, Cin, H, W] contiguous,
+ * y [N, Cout, (H - 3) / 2 + 1, (W - 3) / 2 + 1] with strides ystride.  The arithmetic is pg_conv2d_up2x3_forward's: every float32 operand the exact sum of three
+ * bf16 values (truncation split), a float32 product = the six largest of the nine plane products on v_mfma_f32_32x32x16_bf16, accumulated in float32, smallest
+ * first.  The dropped products (each below 2^-24 of the product) and the behaviour on non-finite operands are as documented for conv2d_up2x3:
+ * the split of +-inf leaves inf - inf = NaN in the second plane, so an infinite operand yields NaN where the fp32 kernel yields +-inf.
+ * `packed_x3` = pg_conv2d_s2x3_pack_weight(packed) with `packed` = pg_conv2d_pack_weight of the OIHW 3x3 kernel; pg_conv2d_s2x3_packed_size(Cout, Cin) BYTES,
+ * 16-byte aligned, once per weight version: [cout group of 128][16-channel chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16, zero
+ * beyond Cout.  Serves Cin % 16 == 0, Cin >= 32, H, W >= 3, one image of x below 2^31 bytes.  x is read in whole aligned 16-byte words: of the memory outside
+ * x only the rest of the 16-byte-aligned words that hold its first and last element is touched.  Fusion: bias, act in {linear, relu, lrelu}, gain, clamp;
+ * any other stage set (residual, in_scale / out_scale, noise, SPADE, x2, statistics, an input pre-activation) -> PG_ERR_UNSUPPORTED before any launch
+ * (callers then use pg_conv2d_forward). */
+int64_t pg_conv2d_s2x3_packed_size(int Cout, int Cin);
+int pg_conv2d_s2x3_pack_weight(const float* packed, void* packed_x3, int Cout, int Cin, void* stream);
+int pg_conv2d_s2x3_forward(const float* x, const void* packed_x3, float* y, int N, int Cin, int H, int W, int Cout, const int64_t ystride[4],
+                           const pg_conv2d_fusion* fusion, void* stream);
 
 /* Streaming 1x1 convolution with few output channels (Cout <= 8; the ToRGB / parsing heads, networks.py:287-316,
  * modulated_conv2d with demodulate=False at networks.py:37-94): float32 NCHW, HW % 4 == 0, 16-byte aligned tensors:

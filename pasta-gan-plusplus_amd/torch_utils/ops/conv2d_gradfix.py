@@ -211,7 +211,8 @@ class _Conv2dMfma(torch.autograd.Function):
             cout = int(weight.shape[0])
             fz = dict(act=ep[0], alpha=ep[1], gain=ep[2], clamp=ep[3] if ep[3] >= 0 else None) if ep is not None else {}
             wg = conv2d_mfma.use_winograd(kh, kw, stride, cout, cin, pad=padding, hw=(h, w), ep=fz)
-            y = conv2d_mfma.conv2d_forward(x, _packed(weight, wg), cout, kh, kw, stride=stride, pad=padding, bias=bias, winograd=wg, **fz)
+            # (s2x3=False: the training route keeps the fp32 kernel for its stride-2 layers -- grad mode is off in here, which is what the inference route's gate reads)
+            y = conv2d_mfma.conv2d_forward(x, _packed(weight, wg), cout, kh, kw, stride=stride, pad=padding, bias=bias, winograd=wg, s2x3=False, **fz)
         else:
             assert ep is None
             cout = int(weight.shape[1])

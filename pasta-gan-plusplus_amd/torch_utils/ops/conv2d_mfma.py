@@ -10,6 +10,7 @@ native layer under this package's ``conv2d_gradfix`` / ``conv2d_resample`` /
 import contextlib
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -153,6 +154,12 @@ def _init(plugin_name='conv2d_plugin'):
         lib.pg_conv2d_stem7x3_pack_weight.argtypes = [vp, vp, i, ctypes.c_float, i, vp]
         lib.pg_conv2d_stem7x3_forward.restype = i
         lib.pg_conv2d_stem7x3_forward.argtypes = [vp, vp, vp, i, i, i, i, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Fusion), vp]
+        lib.pg_conv2d_s2x3_packed_size.restype = i64
+        lib.pg_conv2d_s2x3_packed_size.argtypes = [i, i]
+        lib.pg_conv2d_s2x3_pack_weight.restype = i
+        lib.pg_conv2d_s2x3_pack_weight.argtypes = [vp, vp, i, i, vp]
+        lib.pg_conv2d_s2x3_forward.restype = i
+        lib.pg_conv2d_s2x3_forward.argtypes = [vp, vp, vp, i, i, i, i, i, ctypes.POINTER(i64), ctypes.POINTER(Fusion), vp]
         lib.pg_conv3x3_cin1.restype = i
         lib.pg_conv3x3_cin1.argtypes = [vp, vp, vp, i, i, i, i, f, i, vp]
         lib.pg_conv1x1_small.restype = i
@@ -294,10 +301,38 @@ def pack_weight(w, scale=1.0, flip=False, transpose_oi=False, winograd=False):
     return packed
 
 
+# The stride-2 3x3 convolution with padding 0 (after the FIR pass of a `down = 2` layer) on the bf16 matrix pipe (csrc/conv2d_s2x3.h: three-term operand splits,
+# float32-class).  PG_S2_X3=0 (read at every call, as PG_FIR_SHARED is): the fp32-MFMA kernel everywhere (A/B runs).
+S2_X3 = os.environ.get('PG_S2_X3', '1') != '0'
+_s2x3_of_pack = {}      # id(float32 pack) -> (weakref to it, its bf16 plane stream): made once per weight version, dropped with the pack
+
+
+def s2x3_wanted(n, cin, cout, h, w):
+    """Per-shape policy of the bf16-pipe stride-2 3x3 kernel: the shapes it serves (Cin % 16 == 0, Cin >= 32) minus those where tools/s2x3_probe.py measured it
+    slower than conv2d_mfma<3,3,2> (profiles/s2x3_probe.txt)."""
+    if not S2_X3 or os.environ.get('PG_S2_X3', '1') == '0' or cin % 16 != 0 or cin < 32 or h < 3 or w < 3:
+        return False
+    return True
+
+
+def pack_s2x3(packed32, cout, cin):
+    """The bf16 plane stream of csrc/conv2d_s2x3.h from the float32 pack of a 3x3 kernel (`pack_weight`), cached for as long as that pack lives (the packs are
+    cached per weight version by their owners): [cout group of 128][16-channel chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16."""
+    hit = _s2x3_of_pack.get(id(packed32))
+    if hit is not None and hit[0]() is packed32:
+        return hit[1]
+    lib = _init().lib
+    x3 = torch.empty([lib.pg_conv2d_s2x3_packed_size(cout, cin)], dtype=torch.uint8, device=packed32.device)
+    with torch.cuda.device(packed32.device):
+        nat.check(lib.pg_conv2d_s2x3_pack_weight(nat.ptr(packed32), nat.ptr(x3), cout, cin, nat.stream_of(packed32)), 'pg_conv2d_s2x3_pack_weight')
+    _s2x3_of_pack[id(packed32)] = (weakref.ref(packed32, lambda r, k=id(packed32): _s2x3_of_pack.pop(k, None)), x3)
+    return x3
+
+
 def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y=None, out_step=(1, 1), out_off=(0, 0),
                    in_scale=None, in_bias=None, in_act='linear', in_alpha=0.0, in_gain=1.0, in_clamp=None,
                    out_scale=None, noise=None, noise_gain=1.0, bias=None, act='linear', alpha=0.0, gain=1.0, clamp=None,
-                   residual=None, spade=None, x2=None, winograd=False, stats_eps=None):
+                   residual=None, spade=None, x2=None, winograd=False, stats_eps=None, s2x3=None):
     """One launch of the MFMA convolution (`winograd` = a WINO_* form, True = WINO_F2: of that Winograd kernel; `packed` must then come from
     `pack_weight(..., winograd=<the same form>)`; 3x3 stride 1, dense output, no x2).  `x` [N,Cin,H,W] float32 contiguous; `packed` from
     `pack_weight`.  Writes y[n, co, oy*step+off, ox*step+off] for oy < out_hw[0], ox < out_hw[1]
@@ -307,7 +342,9 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
     (x_norm - mean) * rstd * (1 + gamma) + beta.
     `stats_eps` (F(4x4) one-workgroup launches with the plain tail only: winograd=WINO_F4 / WINO_F4X3, no in_scale / noise / residual / spade; anything else raises
     NativeNotCovered): also gather the instance-norm statistics of the OUTPUT where it is produced -- returns (y, (mean, rstd)) with
-    rstd = 1 / sqrt(var + stats_eps), what `instance_norm_stats(y, stats_eps)` would compute in a second pass over y."""
+    rstd = 1 / sqrt(var + stats_eps), what `instance_norm_stats(y, stats_eps)` would compute in a second pass over y.
+    `s2x3` = False: a stride-2 3x3 launch stays on the fp32 kernel whatever the policy says -- what the forward / backward of an autograd Function passes: grad mode
+    is off inside them, and they ARE the training route (None: `s2x3_wanted` decides when grad mode is off)."""
     lib = _init().lib
     form, label, has_stats_tail, _ = _wino_form(winograd)
     x = _f32c(x, 'x')
@@ -384,7 +421,19 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
         if _timeline is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        if form:
+        # the stride-2 3x3 layer without padding on the bf16 pipe (inference only: the training route keeps the fp32 kernel, as for conv2d_up2x3); a launch the
+        # kernel declines (PG_ERR_UNSUPPORTED) goes to the fp32 kernel below
+        s2x3 = (s2x3 is not False and not form and (kh, kw, int(stride)) == (3, 3, 2) and (int(pad_y), int(pad_x)) == (0, 0) and tuple(out_step) == (1, 1) and tuple(out_off) == (0, 0)
+                and (int(oh), int(ow)) == ((h - 3) // 2 + 1, (w - 3) // 2 + 1) and not torch.is_grad_enabled() and residual is None and spade is None and x2 is None
+                and in_scale is None and in_bias is None and out_scale is None and noise is None and in_act == 'linear' and float(in_gain) == 1.0 and in_clamp is None
+                and act in FUSED_ACTS and s2x3_wanted(n, cin, cout, h, w))
+        st = -2
+        if s2x3:
+            st = lib.pg_conv2d_s2x3_forward(nat.ptr(x), nat.ptr(pack_s2x3(packed, cout, cin)), nat.ptr(y), n, cin, h, w, cout, nat.i64arr(y.stride()), ctypes.byref(fz), nat.stream_of(x))
+            s2x3 = st != -2
+        if s2x3:
+            pass
+        elif form:
             if (kh, kw, int(stride)) != (3, 3, 1) or tuple(out_step) != (1, 1) or tuple(out_off) != (0, 0):
                 raise nat.NativeOpError('conv2d_mfma: winograd=True needs a 3x3 stride-1 dense-output launch')
             st = lib.pg_conv2d_winograd_forward(form, nat.ptr(x), nat.ptr(packed), nat.ptr(y), n, cin, h, w, cout, int(pad_y), int(pad_x),
@@ -404,7 +453,7 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
                                            ctypes.byref(fz), nat.stream_of(x))
         if _timeline is not None:
             ev1.record()
-            _timeline.append(((kh, kw, int(stride), label, f'N{n} {cin}->{cout} {h}x{w}' + (' spade' if spade is not None else '') + (' xf' if in_act != 'linear' else '') + (' mod' if in_scale is not None else '') + (' res' if residual is not None else '')), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1,
+            _timeline.append(((kh, kw, int(stride), label, f'N{n} {cin}->{cout} {h}x{w}' + (' spade' if spade is not None else '') + (' xf' if in_act != 'linear' else '') + (' mod' if in_scale is not None else '') + (' res' if residual is not None else '') + (' s2x3' if s2x3 else '')), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1,
                               4 * (x.numel() + (x2.numel() if x2 is not None else 0) + n * ychan * oh * ow)))
     nat.check(st, 'pg_conv2d_forward')
     if stats_part is not None:
