@@ -2,6 +2,7 @@
 // coefficients, instance-norm statistics, SPADE combine).  The MFMA implicit-GEMM kernel itself
 // lives in conv2d_kernel.h and is instantiated per geometry in conv2d_inst_*.hip.
 #include "conv2d_kernel.h"
+#include "bf16x3.h"
 
 namespace {
 
@@ -106,16 +107,8 @@ struct Wino4PackF4X3 {     // X3 form of conv2d_wino4.h: the float32 value the f
     static __device__ __forceinline__ void store(unsigned short* __restrict__ up, int co, int ci, int a, int b, int nchunks, double ud) {
         const int mb = co >> 6, mt = (co >> 5) & 1, m = co & 31;
         const int k = ci >> 4, cc = ci & 15, j = cc >> 1, h = cc & 1;
-        const float u = (float)ud;
-        const unsigned u0 = __float_as_uint(u) & 0xffff0000u;
-        const float r = u - __uint_as_float(u0);
-        const unsigned u1 = __float_as_uint(r) & 0xffff0000u;
-        const unsigned u2 = __float_as_uint(r - __uint_as_float(u1)) & 0xffff0000u;
         const int64_t unit = ((int64_t)(mb * 2 + mt) * 6 + a) * nchunks + k;
-        const int64_t dst = (((unit * 6 + b) * 3) * 64 + (h * 32 + m)) * 8 + j;                     // plane 0; planes are 64 * 8 words apart
-        up[dst] = (unsigned short)(u0 >> 16);
-        up[dst + 512] = (unsigned short)(u1 >> 16);
-        up[dst + 1024] = (unsigned short)(u2 >> 16);
+        pgconv::x3_store_planes(up, (((unit * 6 + b) * 3) * 64 + (h * 32 + m)) * 8 + j, 64 * 8, (float)ud);
     }
 };
 

@@ -2,10 +2,8 @@
 #include "conv2d_s2x3.h"
 
 /* conv2d(x [N, Cin, H, W], w [Cout, Cin, 3, 3], stride 2, padding 0) -> y [N, Cout, (H - 3) / 2 + 1, (W - 3) / 2 + 1] with the fused bias / activation / gain /
- * clamp of pg_conv2d_forward (networks.py:170-179 around conv2d_resample.py:119-122), float32 operands as exact sums of three bf16 values, the six largest plane
- * products per float32 product on v_mfma_f32_32x32x16_bf16, float32 accumulation, smallest first: float32-class results (csrc/conv2d_s2x3.h).  The dropped
- * products (below 2^-24 of the product) and the behaviour on non-finite operands (the split of +-inf leaves inf - inf = NaN in the second plane: an infinite
- * operand yields NaN where the fp32 kernel yields +-inf) are those documented for conv2d_up2x3.  `packed_x3` = pg_conv2d_s2x3_pack_weight of `packed` (= pg_conv2d_pack_weight of the OIHW 3x3 kernel),
+ * clamp of pg_conv2d_forward (networks.py:170-179 around conv2d_resample.py:119-122), in the three-term bf16 arithmetic of csrc/bf16x3.h (unguarded split: an
+ * infinite operand yields NaN where the fp32 kernel yields +-inf): float32-class results (csrc/conv2d_s2x3.h).  `packed_x3` = pg_conv2d_s2x3_pack_weight of `packed` (= pg_conv2d_pack_weight of the OIHW 3x3 kernel),
  * pg_conv2d_s2x3_packed_size(Cout, Cin) BYTES, once per weight version.  Serves Cin % 16 == 0, Cin >= 32, H, W >= 3; x is read in whole 16-byte words: nothing
  * outside the 16-byte-aligned span that holds x is touched.  Fusion stages other than bias / act in {linear, relu, lrelu} / gain / clamp (a residual, a
  * modulation, SPADE, a second source, noise, statistics) are declined with PG_ERR_UNSUPPORTED before any launch: callers then use pg_conv2d_forward. */
@@ -17,12 +15,7 @@ PG_EXPORT int64_t pg_conv2d_s2x3_packed_size(int Cout, int Cin) {
 PG_EXPORT int pg_conv2d_s2x3_pack_weight(const float* packed, void* packed_x3, int Cout, int Cin, void* stream) {
     if (!packed || !packed_x3 || Cout <= 0 || Cin <= 0 || (((uintptr_t)packed_x3) & 15) != 0) return PG_ERR_INVALID_ARG;
     if (Cin % 16 != 0) return PG_ERR_UNSUPPORTED;
-    const int CoutP32 = (Cout + 31) / 32 * 32, CoutP128 = (Cout + 127) / 128 * 128;
-    const int64_t total = (int64_t)Cin * 9 * CoutP128;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > (int64_t)pg::max_stream_blocks()) blocks = pg::max_stream_blocks();
-    hipLaunchKernelGGL(pgconv::s2x3_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, packed, (unsigned short*)packed_x3, Cin, CoutP128, CoutP32);
-    return pg::launch_status();
+    return pgconv::launch_x3_pack<pgconv::X3PackS2>(packed, packed_x3, Cout, Cin, (hipStream_t)stream);
 }
 
 PG_EXPORT int pg_conv2d_s2x3_forward(const float* x, const void* packed_x3, float* y, int N, int Cin, int H, int W, int Cout, const int64_t ystride[4],

@@ -2,8 +2,8 @@
 #include "conv2d_stem7x3.h"
 
 /* Round 6 -- conv2d(x [N,3,H,W], w [Cout,3,7,7] * scale, stride 1, padding 3) with the fused bias / activation / gain / clamp of pg_conv2d_forward
- * (networks.py:170-179 around conv2d_resample.py:145-147), float32 operands as exact sums of three bf16 values, six plane products per float32 product on
- * v_mfma_f32_32x32x16_bf16, float32 accumulation: float32-class results (csrc/conv2d_stem7x3.h).  `packed` = pg_conv2d_stem7x3_pack_weight of the OIHW
+ * (networks.py:170-179 around conv2d_resample.py:145-147) in the three-term bf16 arithmetic of csrc/bf16x3.h: float32-class results
+ * (csrc/conv2d_stem7x3.h).  `packed` = pg_conv2d_stem7x3_pack_weight of the OIHW
  * kernel (pg_conv2d_stem7x3_packed_size(Cout) BYTES, once per weight version; flip_hw as pg_conv2d_pack_weight).  Fusion stages other than bias / act in
  * {linear, relu, lrelu} / gain / clamp are declined with PG_ERR_UNSUPPORTED (callers then use pg_conv2d_forward). */
 PG_EXPORT int64_t pg_conv2d_stem7x3_packed_size(int Cout) {

@@ -47,8 +47,8 @@ PG_EXPORT int pg_conv2d_up2_forward_splitk(const float* x, const float* packed, 
     return up2_forward(x, packed, y, N, Cin, H, W, Cout, ystride, in_scale, out_scale, workspace, ksplit, stream);
 }
 
-/* Round 6 -- the same layer with its multiplies on the bf16 matrix pipe (csrc/conv2d_up2x3.h): float32 operands as exact sums of three bf16 values, six plane
- * products per float32 product on v_mfma_f32_32x32x16_bf16, float32 accumulation; float32-class results.  `packed_x3` = pg_conv2d_up2x3_pack_weight of `packed`
+/* Round 6 -- the same layer with its multiplies on the bf16 matrix pipe (csrc/conv2d_up2x3.h) in the three-term bf16 arithmetic of csrc/bf16x3.h:
+ * float32-class results.  `packed_x3` = pg_conv2d_up2x3_pack_weight of `packed`
  * (pg_conv2d_up2x3_packed_size(Cout, Cin) bytes), made once per weight version.  Serves W > 16, W % 4 == 0, Cin % 16 == 0, 16-byte aligned x
  * (PG_ERR_UNSUPPORTED otherwise: callers use pg_conv2d_up2_forward); the last output column / row is computed by the fp32 kernel's edge pass. */
 PG_EXPORT int64_t pg_conv2d_up2x3_packed_size(int Cout, int Cin) {
@@ -59,12 +59,7 @@ PG_EXPORT int64_t pg_conv2d_up2x3_packed_size(int Cout, int Cin) {
 PG_EXPORT int pg_conv2d_up2x3_pack_weight(const float* packed, void* packed_x3, int Cout, int Cin, void* stream) {
     if (!packed || !packed_x3 || Cout <= 0 || Cin <= 0) return PG_ERR_INVALID_ARG;
     if (Cin % 16 != 0) return PG_ERR_UNSUPPORTED;
-    const int CoutP = (Cout + 31) / 32 * 32;
-    const int64_t total = (int64_t)Cin * 9 * CoutP;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > (int64_t)pg::max_stream_blocks()) blocks = pg::max_stream_blocks();
-    hipLaunchKernelGGL(pgconv::up2x3_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, packed, (unsigned short*)packed_x3, Cin, CoutP, CoutP);
-    return pg::launch_status();
+    return pgconv::launch_x3_pack<pgconv::X3PackUp2>(packed, packed_x3, Cout, Cin, (hipStream_t)stream);
 }
 
 PG_EXPORT int pg_conv2d_up2x3_forward(const float* x, const float* packed, const void* packed_x3, float* y, int N, int Cin, int H, int W, int Cout,

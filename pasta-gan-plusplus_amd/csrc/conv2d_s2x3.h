@@ -1,7 +1,5 @@
 // The fp32 stride-2 3x3 convolution with padding 0 -- what follows the FIR pass of every `down = 2` 3x3 layer (conv2d_resample.py:119-122 -> conv2d_gradfix.conv2d,
-// stride 2; ResBlock.conv0 and Conv2dLayer, networks.py:170-179) -- with its multiplies on the bf16 matrix pipe, in the arithmetic of conv2d_up2x3.h: every float32
-// operand is the exact sum of three bf16 values (truncation split), a float32 product is the six largest of the nine plane products on v_mfma_f32_32x32x16_bf16,
-// accumulated in float32, smallest first.  Input [N, Cin, 2 OH + 1, 2 OW + 1] (any H, W >= 3: OH = (H - 3) / 2 + 1), output [N, Cout, OH, OW].
+// stride 2; ResBlock.conv0 and Conv2dLayer, networks.py:170-179) -- with its multiplies on the bf16 matrix pipe, in the three-term arithmetic of bf16x3.h.  Input [N, Cin, 2 OH + 1, 2 OW + 1] (any H, W >= 3: OH = (H - 3) / 2 + 1), output [N, Cout, OH, OW].
 //
 // The tile is what makes it pay.  An input sample of a stride-2 layer meets 9/4 taps per cout, not 9, so a staged and split 16-channel chunk has to meet MANY
 // couts before the producers' round (stage, split, one barrier: ~2.7 k cycles whatever it feeds) hides behind the matrix pipe: here all 128 couts of a cout group.
@@ -33,10 +31,11 @@
 //   23 552 .. 82 303   planes [2 buffers][3 planes][2 k-halves][306 records] x 16 B (one buffer 29 376 bytes)
 //   82 304 .. 83 327   bias [2 tiles][128] float32
 // gfx950 compile (hipcc -O3 -Rpass-analysis=kernel-resource-usage): conv2d_s2x3 243 VGPRs, 0 AGPRs, 88 SGPRs, scratch 0 bytes per lane, ZERO spills (VGPR and
-// SGPR), occupancy 2 waves per SIMD = the one 8-wave workgroup; s2x3_pack_kernel 22 VGPRs, no spills.  Of the 243: 108 hold the chunk's weights, 96 the three
+// SGPR), occupancy 2 waves per SIMD = the one 8-wave workgroup.  Of the 243: 108 hold the chunk's weights, 96 the three
 // accumulator pairs, 24 the B ring.
 #pragma once
 #include "conv2d_kernel.h"
+#include "bf16x3_pack.h"
 
 #ifndef SX_EXP
 #define SX_EXP 0         // dev ablations (results wrong by design; tools/s2x3_variants.py): 1 no MFMAs, 2 no operand split, 4 no halo loads, 8 no weight loads, 16 no output stores, 32 cycle stamps of wave 0 into y
@@ -64,19 +63,6 @@ struct S2x3Params {
     int64_t ys[4];
     int act; float alpha, gain, clamp;
 };
-
-typedef __bf16 sx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned sx_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void sx_split_pair(float va, float vb, unsigned& p0, unsigned& p1, unsigned& p2) {      // (conv2d_up2x3.h's ux_split_pair)
-    const unsigned ua = __float_as_uint(va), ub = __float_as_uint(vb);
-    const float ra = va - __uint_as_float(ua & 0xffff0000u), rb = vb - __uint_as_float(ub & 0xffff0000u);
-    const unsigned ura = __float_as_uint(ra), urb = __float_as_uint(rb);
-    const float la = ra - __uint_as_float(ura & 0xffff0000u), lb = rb - __uint_as_float(urb & 0xffff0000u);
-    p0 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-    p1 = __builtin_amdgcn_perm(urb, ura, 0x07060302u);
-    p2 = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
 
 __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sx_smem[];
@@ -184,7 +170,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
                     const int row = ri == 0 ? pw : (ri == 1 ? pw + 4 : 8);
                     const int sh_row = s_sb + (row & 3) * w3;          // + channel * HW: the misalignment of (row, channel), mod 4
                     const float* rp = raw + (reg_w + ri * 160 + (8 * kh) * SX_RW) * 4 + col;
-                    sx_u32x4 pl[3];
+                    x3_u32x4 pl[3];
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         // channel 8 kh + 2 j (+ 1) of the chunk; 16 HW = 0 mod 4, so the chunk does not enter
@@ -192,13 +178,13 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
                         const float va = rp[ca % 8 * 40 + ((sh_row + ca * hw3) & 3)], vb = rp[cb % 8 * 40 + ((sh_row + cb * hw3) & 3)];
                         unsigned p0, p1, p2;
                         if (SX_EXP & 2) { p0 = __float_as_uint(va); p1 = __float_as_uint(vb); p2 = p0; }
-                        else sx_split_pair(va, vb, p0, p1, p2);
+                        else x3_split_pair(va, vb, p0, p1, p2);
                         pl[0][j] = p0; pl[1][j] = p1; pl[2][j] = p2;
                     }
                     unsigned char* dst = pl_b + (size_t)(kh * SX_NPIX + row * SX_PR + (col & 1) * 17 + (col >> 1)) * 16;
-                    *(sx_u32x4*)(dst) = pl[0];
-                    *(sx_u32x4*)(dst + SX_PLB) = pl[1];
-                    *(sx_u32x4*)(dst + 2 * SX_PLB) = pl[2];
+                    *(x3_u32x4*)(dst) = pl[0];
+                    *(x3_u32x4*)(dst + SX_PLB) = pl[1];
+                    *(x3_u32x4*)(dst + 2 * SX_PLB) = pl[2];
                 }
             }
             if (++s_chunk == nchunks) { s_chunk = 0; s_tile += gridDim.x; s_par ^= 1; }
@@ -220,7 +206,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
     const int half = lane >> 5, l31 = lane & 31;
     const int orow = l31 >> 4, ocol = l31 & 15;                        // this lane's D column: output row (of the accumulator's two) and column
     f32x16 acc[2], accs[2];                                            // per accumulator tile: the sum of the leading products a0 b0 (joined chunk by chunk), and the five small product classes
-    sx_u32x4 A[9][3];                                                  // the current chunk's weights [tap][plane]; reloaded tap by tap with the next chunk's
+    x3_u32x4 A[9][3];                                                  // the current chunk's weights [tap][plane]; reloaded tap by tap with the next chunk's
     auto wslab = [&](int grp, int chunk) __attribute__((always_inline)) {
         return p.wx3 + (((int64_t)grp * nchunks + chunk) * 4 + wave) * (int64_t)SX_WSLAB + lane * 16;
     };
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
 #pragma unroll
         for (int t = 0; t < 9; t++)
 #pragma unroll
-            for (int pl = 0; pl < 3; pl++) A[t][pl] = (SX_EXP & 8) ? (sx_u32x4){0u, 0u, 0u, 0u} : *(const sx_u32x4*)(w0 + (t * 3 + pl) * SX_FRAG);
+            for (int pl = 0; pl < 3; pl++) A[t][pl] = (SX_EXP & 8) ? (x3_u32x4){0u, 0u, 0u, 0u} : *(const x3_u32x4*)(w0 + (t * 3 + pl) * SX_FRAG);
         // the first chunk's weights are home before the loops: whatever order the loads above were issued in, the waits inside the chunk loop then count the
         // loop's own reloads only (a load still pending at the loop's entry makes every round wait for the count of the worst entry order)
         __builtin_amdgcn_s_waitcnt(0x0f70);                            // vmcnt(0)
@@ -264,11 +250,10 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
                 // tap (ky, kx) of accumulator a reads halo row 4 a + 2 orow + ky, halo column 2 ocol + kx = record (kx & 1) * 17 + ocol + (kx >> 1) of that row
                 auto b_frag = [&](int t, int a, int pl) __attribute__((always_inline)) {
                     const int ky = t / 3, kx = t % 3;
-                    return *(const sx_u32x4*)(bb + (size_t)pl * SX_PLB + (size_t)((4 * a + ky) * SX_PR + (kx & 1) * 17 + (kx >> 1)) * 16);
+                    return *(const x3_u32x4*)(bb + (size_t)pl * SX_PLB + (size_t)((4 * a + ky) * SX_PR + (kx & 1) * 17 + (kx >> 1)) * 16);
                 };
-                constexpr int PA[6] = {2, 1, 1, 0, 0, 0}, PB[6] = {0, 1, 0, 2, 1, 0};        // small products first
                 // B ring of two slots of one accumulator's three planes: slot (2 t + a) & 1 = a, requested six MFMAs (one accumulator's share of a tap) ahead
-                sx_u32x4 B[2][3];
+                x3_u32x4 B[2][3];
                 f32x16 accp[2];                                        // this chunk's leading products
 #pragma unroll
                 for (int a = 0; a < 2; a++)
@@ -292,15 +277,15 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
                             // tile's sum by one VALU addition per chunk: the MFMA's accumulation is less exact than a rounded addition (measured: with everything
                             // in one accumulator 1.7 - 3.6 x the fp32 kernel's error against float64, leading and small apart 2.5 x at 128 channels; the bar is 2 x).
                             f32x16& dacc = pr == 5 ? accp[a] : accs[a];
-                            if (!(SX_EXP & 1) || A[t][PA[pr]][0] == 0x12345678u)
-                                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sx_bf16x8, A[t][PA[pr]]), __builtin_bit_cast(sx_bf16x8, B[a][PB[pr]]), dacc, 0, 0, 0);
+                            if (!(SX_EXP & 1) || A[t][X3_PA[pr]][0] == 0x12345678u)
+                                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x3_bf16x8, A[t][X3_PA[pr]]), __builtin_bit_cast(x3_bf16x8, B[a][X3_PB[pr]]), dacc, 0, 0, 0);
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     // this tap's fragments have issued their last MFMA of the chunk: the next chunk's take their place
                     if (!(SX_EXP & 8)) {
 #pragma unroll
-                        for (int pl = 0; pl < 3; pl++) A[t][pl] = *(const sx_u32x4*)(wn + (t * 3 + pl) * SX_FRAG);
+                        for (int pl = 0; pl < 3; pl++) A[t][pl] = *(const x3_u32x4*)(wn + (t * 3 + pl) * SX_FRAG);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -365,25 +350,15 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
     }
 }
 
-// wp32 = pg_conv2d_pack_weight's [Cin][9][CoutP32] float32 pack of the 3x3 kernel (weight gain folded in) -> the bf16 plane stream
-// [cout group][chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels], zero beyond Cout
-__global__ __launch_bounds__(256) void s2x3_pack_kernel(const float* __restrict__ wp32, unsigned short* __restrict__ out, int Cin, int CoutP128, int CoutP32) {
-    const int nchunks = Cin / SX_KC;
-    const int64_t total = (int64_t)Cin * 9 * CoutP128;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int co = (int)(i % CoutP128), tap = (int)((i / CoutP128) % 9), ci = (int)(i / ((int64_t)CoutP128 * 9));
-        const float v = co < CoutP32 ? wp32[((int64_t)ci * 9 + tap) * CoutP32 + co] : 0.f;
-        const unsigned u0 = __float_as_uint(v) & 0xffff0000u;
-        const float r = v - __uint_as_float(u0);
-        const unsigned u1 = __float_as_uint(r) & 0xffff0000u;
-        const unsigned u2 = __float_as_uint(r - __uint_as_float(u1)) & 0xffff0000u;
+// The weight stream of this kernel for x3_pack_kernel: [cout group][chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels], zero-padded to whole groups
+struct X3PackS2 {
+    static constexpr int PLANE = 512;
+    static int cout_padded(int Cout) { return (Cout + SX_GROUP - 1) / SX_GROUP * SX_GROUP; }
+    static __device__ __forceinline__ int64_t dst(int co, int tap, int ci, int nchunks) {
         const int grp = co >> 7, mb = (co >> 5) & 3, m = co & 31, chunk = ci >> 4, kh = (ci >> 3) & 1, j = ci & 7;
-        const int64_t dst = ((((((int64_t)grp * nchunks + chunk) * 4 + mb) * 9 + tap) * 3) * 2 + kh) * 256 + m * 8 + j;      // plane 0; planes are 512 values apart
-        out[dst] = (unsigned short)(u0 >> 16);
-        out[dst + 512] = (unsigned short)(u1 >> 16);
-        out[dst + 1024] = (unsigned short)(u2 >> 16);
+        return ((((((int64_t)grp * nchunks + chunk) * 4 + mb) * 9 + tap) * 3) * 2 + kh) * 256 + m * 8 + j;
     }
-}
+};
 
 inline int64_t s2x3_packed_bytes(int Cout, int Cin) { return (int64_t)((Cout + SX_GROUP - 1) / SX_GROUP) * (Cin / SX_KC) * 4 * SX_WSLAB; }
 

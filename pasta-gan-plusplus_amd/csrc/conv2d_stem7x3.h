@@ -1,6 +1,5 @@
 // The 7x7, three-channel stem convolution of the garment encoder (networks.py:2233-2238 `spade_encoder[0]`: Conv2dLayer(3, 64, kernel_size=7), stride 1, pad 3)
-// with its multiplies on the bf16 matrix pipe (round 6): every float32 operand the exact sum of three bf16 values (truncation split), a float32 product = the six
-// largest plane products on v_mfma_f32_32x32x16_bf16 with float32 accumulation -- float32-class results (conv2d_up2x3.h, conv2d_wino4.h X3 form).
+// with its multiplies on the bf16 matrix pipe (round 6) in the three-term arithmetic of bf16x3.h (the six products in this kernel's own order, PA6 / PB6 below).
 // The layer is 39.5 GFLOP at N = 8, 512^2: 251 us at the fp32 matrix peak, 452 us measured on conv2d_mfma<7,7,1,64,2,0>; its output is 537 MB (~110 us of HBM).
 //
 //   * K order = (kx, ci, ky): 21 groups of 8 (seven rows ky + one zero weight), 168 -> 11 MFMA K steps (the last half step all zero).  A lane's B operand of a
@@ -15,6 +14,7 @@
 //   * epilogue = pg_conv2d_forward's for the stages this layer uses: bias, linear | relu | lrelu, gain, clamp.  Anything else is declined.
 #pragma once
 #include "conv2d_kernel.h"
+#include "bf16x3.h"
 
 #ifndef S7_EXP
 #define S7_EXP 0          // dev ablations (results wrong by design; tools/stem7_variants.py): 1 no record updates, 2 no output stores, 4 no MFMAs, 8 no B-operand reads
@@ -31,17 +31,6 @@ struct Stem7Params {
     int64_t ys[4];
     int act; float alpha, gain, clamp;
 };
-
-typedef __bf16 s7_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned s7_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void s7_split(float v, unsigned& b0, unsigned& b1, unsigned& b2) {      // three bf16 terms in the low halves
-    const unsigned h0 = __float_as_uint(v) & 0xffff0000u;
-    const float r = v - __uint_as_float(h0);
-    const unsigned h1 = __float_as_uint(r) & 0xffff0000u;
-    const float r2 = r - __uint_as_float(h1);
-    b0 = h0 >> 16; b1 = h1 >> 16; b2 = __float_as_uint(r2) >> 16;
-}
 
 __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s7_smem[];
@@ -61,13 +50,13 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
     const float* xin = p.x + (int64_t)n * 3 * HW;
 
     // ---- this wave's weights: [m-tile][K step][plane][lane] x 16 B
-    s7_u32x4 A[S7_KS][3];
+    x3_u32x4 A[S7_KS][3];
     {
         const unsigned char* wb = p.wx3 + ((int64_t)(mp * 2 + mt) * S7_KS * 3 * 64 + lane) * 16;
 #pragma unroll
         for (int ks = 0; ks < S7_KS; ks++)
 #pragma unroll
-            for (int pl = 0; pl < 3; pl++) A[ks][pl] = *(const s7_u32x4*)(wb + (size_t)(ks * 3 + pl) * 64 * 16);
+            for (int pl = 0; pl < 3; pl++) A[ks][pl] = *(const x3_u32x4*)(wb + (size_t)(ks * 3 + pl) * 64 * 16);
     }
 
     // ---- records of row y0: rows y0 - 3 .. y0 + 4.  A record task = (channel, column): 3 x 262 = 786 of them, at most two per thread (task = tid, tid + 512;
@@ -86,19 +75,19 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         if (rec_off[q] >= 0) {
-            s7_u32x4 r[3] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+            x3_u32x4 r[3] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int row = y0 - 3 + j;
                 const float v = (voff[q] != 0x80000000u && row >= 0 && row < p.H) ? xin[(voff[q] >> 2) + row * p.W] : 0.f;
                 unsigned b0, b1, b2;
-                s7_split(v, b0, b1, b2);
+                x3_split(v, b0, b1, b2);
                 r[0][j >> 1] |= b0 << (16 * (j & 1));
                 r[1][j >> 1] |= b1 << (16 * (j & 1));
                 r[2][j >> 1] |= b2 << (16 * (j & 1));
             }
 #pragma unroll
-            for (int pl = 0; pl < 3; pl++) *(s7_u32x4*)(s7_smem + (size_t)(pl * 3 * S7_NCOL * 16 + rec_off[q])) = r[pl];
+            for (int pl = 0; pl < 3; pl++) *(x3_u32x4*)(s7_smem + (size_t)(pl * 3 * S7_NCOL * 16 + rec_off[q])) = r[pl];
         }
     }
     float* smp_s = (float*)(s7_smem + 2 * S7_REC_B);          // [2 tasks][512 threads] samples of the row being inserted (LDS-DMA)
@@ -158,17 +147,17 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
             for (int q = 0; q < 2; q++) {
                 if (rec_off[q] >= 0) {
                     unsigned b[3];
-                    s7_split(smp_s[512 * q + tid], b[0], b[1], b[2]);
+                    x3_split(smp_s[512 * q + tid], b[0], b[1], b[2]);
 #pragma unroll
                     for (int pl = 0; pl < 3; pl++) {
                         const size_t ro = (size_t)(pl * 3 * S7_NCOL * 16 + rec_off[q]);
-                        const s7_u32x4 r = *(const s7_u32x4*)(cur + ro);
-                        s7_u32x4 o;
+                        const x3_u32x4 r = *(const x3_u32x4*)(cur + ro);
+                        x3_u32x4 o;
                         o[0] = __builtin_amdgcn_alignbit(r[1], r[0], 16);
                         o[1] = __builtin_amdgcn_alignbit(r[2], r[1], 16);
                         o[2] = __builtin_amdgcn_alignbit(r[3], r[2], 16);
                         o[3] = __builtin_amdgcn_alignbit(b[pl], r[3], 16);
-                        *(s7_u32x4*)(nb + ro) = o;
+                        *(x3_u32x4*)(nb + ro) = o;
                     }
                 }
             }
@@ -187,9 +176,9 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
             return cur + (half ? off1 : off0) + (size_t)(32 * bq + l31) * 16;
         };
         auto b_load = [&](const unsigned char* bb, int pl, int bi) __attribute__((always_inline)) {
-            return *(const s7_u32x4*)(bb + (size_t)(pl * 3 * S7_NCOL + 128 * bi) * 16);
+            return *(const x3_u32x4*)(bb + (size_t)(pl * 3 * S7_NCOL + 128 * bi) * 16);
         };
-        s7_u32x4 B0[2], B0n[2], B1[2], B2[2];
+        x3_u32x4 B0[2], B0n[2], B1[2], B2[2];
         {
             const unsigned char* bb = b_addr(0);
             B0[0] = b_load(bb, 0, 0); B0[1] = b_load(bb, 0, 1);
@@ -209,9 +198,9 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
             for (int pr = 0; pr < 6; pr++)
 #pragma unroll
                 for (int bi = 0; bi < 2; bi++) {
-                    const s7_u32x4 bv = (S7_EXP & 8) ? A[ks][PB6[pr]] : (PB6[pr] == 0 ? B0[bi] : (PB6[pr] == 1 ? B1[bi] : B2[bi]));
+                    const x3_u32x4 bv = (S7_EXP & 8) ? A[ks][PB6[pr]] : (PB6[pr] == 0 ? B0[bi] : (PB6[pr] == 1 ? B1[bi] : B2[bi]));
                     if (!(S7_EXP & 4) || bv[0] == 0x12345678u)
-                        acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s7_bf16x8, A[ks][PA6[pr]]), __builtin_bit_cast(s7_bf16x8, bv), acc[bi], 0, 0, 0);
+                        acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x3_bf16x8, A[ks][PA6[pr]]), __builtin_bit_cast(x3_bf16x8, bv), acc[bi], 0, 0, 0);
                 }
             __builtin_amdgcn_sched_barrier(0);
             B0[0] = B0n[0]; B0[1] = B0n[1];
@@ -249,14 +238,7 @@ __global__ __launch_bounds__(256) void stem7x3_pack_kernel(const float* __restri
             const int kx = g / 3, ci = g % 3, ky = j;
             v = w[((co * 3 + ci) * 7 + (flip ? 6 - ky : ky)) * 7 + (flip ? 6 - kx : kx)] * scale;
         }
-        const unsigned u0 = __float_as_uint(v) & 0xffff0000u;
-        const float r = v - __uint_as_float(u0);
-        const unsigned u1 = __float_as_uint(r) & 0xffff0000u;
-        const unsigned u2 = __float_as_uint(r - __uint_as_float(u1)) & 0xffff0000u;
-        const int64_t dst = ((((int64_t)mtile * S7_KS + ks) * 3) * 64 + lane) * 8 + j;      // plane 0; planes are 64 * 8 words apart
-        out[dst] = (unsigned short)(u0 >> 16);
-        out[dst + 512] = (unsigned short)(u1 >> 16);
-        out[dst + 1024] = (unsigned short)(u2 >> 16);
+        x3_store_planes(out, ((((int64_t)mtile * S7_KS + ks) * 3) * 64 + lane) * 8 + j, 64 * 8, v);
     }
 }
 

@@ -1,7 +1,5 @@
 // The fp32 `up = 2` layer (conv2d_up2.h: stride-2 transposed 3x3 convolution, all four output parities in one pass) with its multiplies on the bf16 matrix
-// pipe (round 6): every float32 operand is the exact sum of three bf16 values (truncation split, 8 + 8 + 8 significand bits) and a float32 product is
-// evaluated as the six largest of the nine plane products on v_mfma_f32_32x32x16_bf16 with float32 accumulation -- float32-class results (the dropped
-// products are below 2^-24 of the product) at 6/16 of the fp32 MFMA's issue time.  Reference: conv2d_resample.py:125-142 -> conv2d_gradfix.conv_transpose2d
+// pipe (round 6) in the three-term arithmetic of bf16x3.h: float32-class results at 6/16 of the fp32 MFMA's issue time.  Reference: conv2d_resample.py:125-142 -> conv2d_gradfix.conv_transpose2d
 // (stride 2), networks.py:73-94 for the modulation around it.
 //
 // Why this pays here and barely did in the Winograd kernel (conv2d_wino4.h, X3 form: +8 %): there a transformed value meets 64 couts once; here an input sample
@@ -22,6 +20,7 @@
 #pragma once
 #include "conv2d_up2.h"
 #include "conv2d_up2_edges.h"
+#include "bf16x3_pack.h"
 
 #ifndef UX_EXP
 #define UX_EXP 0         // dev ablations (results wrong by design; tools/up2x3_variants.py): 1 no MFMAs, 2 no operand split, 4 no halo loads, 8 no weight DMA, 16 no output stores, 64 edge columns read contiguously, 128 no edge pass
@@ -41,19 +40,6 @@ constexpr int UX_WPT = (UX_WW + 255) / 256;                           // 7
 constexpr int UX_WBUF = UX_WPT * 256 * 16;                            // bytes
 constexpr int UX_TASKS = UX_NPIX * 2;                                 // split tasks per chunk: (pixel, k-half)
 constexpr int UX_TPT = (UX_TASKS + 255) / 256;                        // 3 per thread
-
-typedef __bf16 ux_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned ux_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void ux_split_pair(float va, float vb, unsigned& p0, unsigned& p1, unsigned& p2) {
-    const unsigned ua = __float_as_uint(va), ub = __float_as_uint(vb);
-    const float ra = va - __uint_as_float(ua & 0xffff0000u), rb = vb - __uint_as_float(ub & 0xffff0000u);
-    const unsigned ura = __float_as_uint(ra), urb = __float_as_uint(rb);
-    const float la = ra - __uint_as_float(ura & 0xffff0000u), lb = rb - __uint_as_float(urb & 0xffff0000u);
-    p0 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-    p1 = __builtin_amdgcn_perm(urb, ura, 0x07060302u);
-    p2 = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
 
 template <bool MOD>
 __global__ __launch_bounds__(512, 1) void conv2d_up2x3(Up2Params p, const unsigned char* __restrict__ wx3, float* __restrict__ xcol) {
@@ -159,20 +145,20 @@ __global__ __launch_bounds__(512, 1) void conv2d_up2x3(Up2Params p, const unsign
                     const int kh = rem >= 33 ? 1 : 0, col = rem - 33 * kh;
                     const int row = ri == 0 ? pw : (ri == 1 ? pw + 4 : 8);
                     const float* rp = raw + (reg_w + ri * 160 + (8 * kh) * 10) * 4 + col + 3;     // halo column c sits at column c + 3 of the 40-float row
-                    ux_u32x4 pl[3];
+                    x3_u32x4 pl[3];
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         float va = rp[(2 * j) * 40], vb = rp[(2 * j + 1) * 40];
                         if (MOD) { va *= cs[8 * kh + 2 * j]; vb *= cs[8 * kh + 2 * j + 1]; }
                         unsigned p0, p1, p2;
                         if (UX_EXP & 2) { p0 = __float_as_uint(va); p1 = __float_as_uint(vb); p2 = p0; }
-                        else ux_split_pair(va, vb, p0, p1, p2);
+                        else x3_split_pair(va, vb, p0, p1, p2);
                         pl[0][j] = p0; pl[1][j] = p1; pl[2][j] = p2;
                     }
                     unsigned char* dst = pl_b + (size_t)(kh * UX_NPIX + row * UX_PW + col) * 16;      // [k-half][pixel]
-                    *(ux_u32x4*)(dst) = pl[0];
-                    *(ux_u32x4*)(dst + UX_PLB) = pl[1];
-                    *(ux_u32x4*)(dst + 2 * UX_PLB) = pl[2];
+                    *(x3_u32x4*)(dst) = pl[0];
+                    *(x3_u32x4*)(dst + UX_PLB) = pl[1];
+                    *(x3_u32x4*)(dst + 2 * UX_PLB) = pl[2];
                 }
             }
             if (++s_chunk == nchunks) { s_chunk = 0; s_par ^= 1; }
@@ -237,23 +223,22 @@ __global__ __launch_bounds__(512, 1) void conv2d_up2x3(Up2Params p, const unsign
             {
                 const unsigned char* ab = wbuf + (size_t)wb * UX_WBUF + (size_t)(half * 32 + l31) * 16;
                 const unsigned char* bb = planes + (size_t)wb * 3 * UX_PLB + (size_t)(half * UX_NPIX + (2 * wave) * UX_PW + l31) * 16;
-                ux_u32x4 B[3][2][3];                                   // B[halo row of the wave 0..2][column l31 + cc][plane]
+                x3_u32x4 B[3][2][3];                                   // B[halo row of the wave 0..2][column l31 + cc][plane]
 #pragma unroll
                 for (int pl = 0; pl < 3; pl++)
 #pragma unroll
                     for (int hr = 0; hr < 3; hr++)
 #pragma unroll
-                        for (int cc = 0; cc < 2; cc++) B[hr][cc][pl] = *(const ux_u32x4*)(bb + (size_t)pl * UX_PLB + (size_t)(hr * UX_PW + cc) * 16);
+                        for (int cc = 0; cc < 2; cc++) B[hr][cc][pl] = *(const x3_u32x4*)(bb + (size_t)pl * UX_PLB + (size_t)(hr * UX_PW + cc) * 16);
                 // tap id 3 ky + kx: taps 0, 2, 6, 8 -> parity (0,0) on x[q][r], x[q][r-1], x[q-1][r], x[q-1][r-1]; taps 1, 7 -> (0,1) on x[q][r], x[q-1][r];
                 // taps 3, 5 -> (1,0) on x[q][r], x[q][r-1]; tap 4 -> (1,1) on x[q][r].  Steps of three taps; within a step and across steps the same accumulator
                 // is at least four MFMAs apart (a dependent 32x32x16 link costs ~87 cycles).
                 constexpr int TAPS[9] = {0, 1, 3, 2, 7, 5, 6, 4, 8};
                 constexpr int PAR[9] = {0, 1, 0, 2, 3, 2, 0, 1, 0}, DY[9] = {1, 1, 1, 1, 1, 1, 0, 0, 0}, CC[9] = {1, 1, 0, 1, 1, 0, 1, 1, 0};
-                constexpr int PA[6] = {2, 1, 1, 0, 0, 0}, PB[6] = {0, 1, 0, 2, 1, 0};        // small products first
                 auto a_frag = [&](int pr, int ti3, int j) __attribute__((always_inline)) {
-                    return *(const ux_u32x4*)(ab + (size_t)((TAPS[3 * ti3 + j] * 3 + PA[pr]) * 64) * 16);
+                    return *(const x3_u32x4*)(ab + (size_t)((TAPS[3 * ti3 + j] * 3 + X3_PA[pr]) * 64) * 16);
                 };
-                ux_u32x4 Ar[3][3];                                     // ring of three steps' A fragments: step st in slot st % 3, requested two steps ahead
+                x3_u32x4 Ar[3][3];                                     // ring of three steps' A fragments: step st in slot st % 3, requested two steps ahead
 #pragma unroll
                 for (int j = 0; j < 3; j++) { Ar[0][j] = a_frag(0, 0, j); Ar[1][j] = a_frag(0, 1, j); }
 #pragma unroll
@@ -269,8 +254,8 @@ __global__ __launch_bounds__(512, 1) void conv2d_up2x3(Up2Params p, const unsign
                         const int tp = TAPS[3 * ti3 + j];
 #pragma unroll
                         for (int nt = 0; nt < 2; nt++) {
-                            if (!(UX_EXP & 1) || Ar[st % 3][j][0] == 0x12345678u) acc[PAR[tp]][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ux_bf16x8, Ar[st % 3][j]),
-                                                                                       __builtin_bit_cast(ux_bf16x8, B[nt + DY[tp]][CC[tp]][PB[pr]]), acc[PAR[tp]][nt], 0, 0, 0);
+                            if (!(UX_EXP & 1) || Ar[st % 3][j][0] == 0x12345678u) acc[PAR[tp]][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x3_bf16x8, Ar[st % 3][j]),
+                                                                                       __builtin_bit_cast(x3_bf16x8, B[nt + DY[tp]][CC[tp]][X3_PB[pr]]), acc[PAR[tp]][nt], 0, 0, 0);
                             __builtin_amdgcn_sched_barrier(0);         // (keep the issue order: the same accumulator at least four MFMAs apart)
                         }
                     }
@@ -325,24 +310,15 @@ __global__ __launch_bounds__(512, 1) void conv2d_up2x3(Up2Params p, const unsign
     }
 }
 
-// wp32 = pg_conv2d_pack_weight's [CinP][9][CoutP] float32 pack (weight gain / flip folded in) -> the X3 slabs
-__global__ __launch_bounds__(256) void up2x3_pack_kernel(const float* __restrict__ wp32, unsigned short* __restrict__ out, int Cin, int CoutP32, int CoutP) {
-    const int nchunks = Cin / UX_KC;
-    const int64_t total = (int64_t)Cin * 9 * CoutP32;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int co = (int)(i % CoutP32), tap = (int)((i / CoutP32) % 9), ci = (int)(i / ((int64_t)CoutP32 * 9));
-        const float v = co < CoutP ? wp32[((int64_t)ci * 9 + tap) * CoutP + co] : 0.f;
-        const unsigned u0 = __float_as_uint(v) & 0xffff0000u;
-        const float r = v - __uint_as_float(u0);
-        const unsigned u1 = __float_as_uint(r) & 0xffff0000u;
-        const unsigned u2 = __float_as_uint(r - __uint_as_float(u1)) & 0xffff0000u;
+// The weight slabs of this kernel for x3_pack_kernel: [m-block 32][chunk][tap 9][plane 3][k-half 2][32 couts][8 channels]
+struct X3PackUp2 {
+    static constexpr int PLANE = 512;
+    static int cout_padded(int Cout) { return (Cout + U_BM - 1) / U_BM * U_BM; }
+    static __device__ __forceinline__ int64_t dst(int co, int tap, int ci, int nchunks) {
         const int mb = co >> 5, m = co & 31, chunk = ci >> 4, kh = (ci >> 3) & 1, j = ci & 7;
-        const int64_t dst = ((((((int64_t)mb * nchunks + chunk) * 9 + tap) * 3) * 2 + kh) * 32 + m) * 8 + j;      // plane 0; planes are 2 * 32 * 8 words apart
-        out[dst] = (unsigned short)(u0 >> 16);
-        out[dst + 512] = (unsigned short)(u1 >> 16);
-        out[dst + 1024] = (unsigned short)(u2 >> 16);
+        return ((((((int64_t)mb * nchunks + chunk) * 9 + tap) * 3) * 2 + kh) * 32 + m) * 8 + j;
     }
-}
+};
 
 inline size_t up2x3_lds_bytes(int Cin) { return (size_t)UX_RAW * 4 + 2 * 3 * (size_t)UX_PLB + 2 * (size_t)UX_WBUF + ((size_t)2 * Cin + 2 * U_BM) * 4; }
 

@@ -16,6 +16,7 @@
 //
 // Roofline: MFMA.  Algorithmic FLOPs = 2 * N * OH * OW * Cout * Cin * KH * KW (the forward pass's count) against 157.3 TFLOP/s.
 #include "conv2d_kernel.h"        // LDS-DMA helpers (dma_dword, lds_offset)
+#include "bf16x3.h"
 
 namespace {
 
@@ -1005,16 +1006,7 @@ __global__ __launch_bounds__(256) void split3_bf16_cl_kernel(const float* __rest
         for (int d = 0; d < 4; d++) {
             unsigned h2[2], m2[2], l2[2];
 #pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const float v = tile[cg + 2 * d + e][px];
-                const unsigned hb = __builtin_bit_cast(unsigned, v) & 0xffff0000u;
-                // a non-finite value keeps its leading plane and gets zero remainders (inf - inf would turn an overflow into NaN where the fp32 kernel keeps +-inf: ADVICE r5)
-                const bool fin = (hb & 0x7f800000u) != 0x7f800000u;
-                const float r = fin ? v - __builtin_bit_cast(float, hb) : 0.f;
-                const unsigned mb = __builtin_bit_cast(unsigned, r) & 0xffff0000u;
-                const float r2 = r - __builtin_bit_cast(float, mb);
-                h2[e] = hb >> 16; m2[e] = mb >> 16; l2[e] = __builtin_bit_cast(unsigned, r2) >> 16;
-            }
+            for (int e = 0; e < 2; e++) pgconv::x3_split_guarded(tile[cg + 2 * d + e][px], h2[e], m2[e], l2[e]);      // (an overflow in dy stays +-inf: bf16x3.h)
             hi[d] = h2[0] | (h2[1] << 16); mid[d] = m2[0] | (m2[1] << 16); lo[d] = l2[0] | (l2[1] << 16);
         }
         unsigned short* o = out + (((int64_t)n * HW + p0 + px) * C + c0 + cg);

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "conv2d_wino.h"
+#include "bf16x3.h"
 
 #ifndef WINO4_EXP
 #define WINO4_EXP 0      // dev ablations (results wrong by design): 1 no U loads, 2 no transform phase, 4 no tail, 8 no halo DMA, 16 no output stores,
@@ -66,20 +67,6 @@ constexpr int W4_UGROUP = 3 * 1024;              // bytes of one A-operand group
 constexpr int W4_UCHUNK = 4 * W4_UGROUP;         // per (wave unit = (m-block, mt, a), chunk): groups (jg, quad)
 constexpr int W4_EX = 6 * 16 * 32 * 4;           // exchange floats per round: [a][cout 16][tile 32][4 columns]
 constexpr int W4_UCHUNK_X3 = 6 * W4_UGROUP;      // X3 form: per (wave unit, chunk) six groups (b), each three planes x 64 lanes x 16 B (8 bf16 channels)
-typedef __bf16 w4_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned w4_u32x4 __attribute__((ext_vector_type(4)));
-
-// X3 form: a float32 value is the exact sum of three bf16 values (8 + 8 + 8 significand bits, by truncation).  Two values of adjacent K slots -> the three
-// packed operand words (plane 0 = leading bits, 1 = middle, 2 = trailing), low half = the first value: 4 v_and + 4 v_sub + 3 v_perm per pair.
-__device__ __forceinline__ void w4_split_pair(float va, float vb, unsigned& p0, unsigned& p1, unsigned& p2) {
-    const unsigned ua = __float_as_uint(va), ub = __float_as_uint(vb);
-    const float ra = va - __uint_as_float(ua & 0xffff0000u), rb = vb - __uint_as_float(ub & 0xffff0000u);
-    const unsigned ura = __float_as_uint(ra), urb = __float_as_uint(rb);
-    const float la = ra - __uint_as_float(ura & 0xffff0000u), lb = rb - __uint_as_float(urb & 0xffff0000u);
-    p0 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-    p1 = __builtin_amdgcn_perm(urb, ura, 0x07060302u);
-    p2 = __builtin_amdgcn_perm(__float_as_uint(lb), __float_as_uint(la), 0x07060302u);
-}
 
 // 1-D transforms.  B^T rows (input), A^T rows (output) of F(4,3) with points 0, 1, -1, 2, -2, inf.
 __device__ __forceinline__ void w4_bt(float d0, float d1, float d2, float d3, float d4, float d5,
@@ -457,12 +444,12 @@ __global__ __launch_bounds__(768, 3) void conv2d_wino4(ConvParams p) {
 #pragma unroll
                     for (int j = 0; j < 8; j++) dst[j] = vb[b * 512 + j * 64];
                 };
-                w4_u32x4 bp[2][3];
+                x3_u32x4 bp[2][3];
                 read_b8(0, br);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     unsigned p0, p1, p2;
-                    w4_split_pair(br[2 * q], br[2 * q + 1], p0, p1, p2);
+                    x3_split_pair(br[2 * q], br[2 * q + 1], p0, p1, p2);
                     bp[0][0][q] = p0; bp[0][1][q] = p1; bp[0][2][q] = p2;
                 }
                 read_b8(1, br);
@@ -477,17 +464,15 @@ __global__ __launch_bounds__(768, 3) void conv2d_wino4(ConvParams p) {
                     } else wait_u(ur[g & 1], g < 2 && dma_q);
                     W4_XSTAMP(2 + 3 * g);
                     __builtin_amdgcn_sched_barrier(0);
-                    // small products first:  u2 v0,  u1 v1,  u1 v0,  u0 v2,  u0 v1,  u0 v0
-                    constexpr int PA[6] = {2, 1, 1, 0, 0, 0}, PB[6] = {0, 1, 0, 2, 1, 0};
 #pragma unroll
                     for (int t = 0; t < 6; t++) {
-                        if (!(W4X_EXP & 8) || bp[0][0][0] == 0x12345678u) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(w4_bf16x8, ur[g & 1][PA[t]]), __builtin_bit_cast(w4_bf16x8, bp[g & 1][PB[t]]),
+                        if (!(W4X_EXP & 8) || bp[0][0][0] == 0x12345678u) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x3_bf16x8, ur[g & 1][X3_PA[t]]), __builtin_bit_cast(x3_bf16x8, bp[g & 1][X3_PB[t]]),
                                                                          (FIRST && t == 0) ? zero16 : acc[g], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
                         if (g + 1 < 6 && t < 4) {
                             unsigned p0, p1, p2;
                             if (W4X_EXP & 4) { p0 = __float_as_uint(br[2 * t]); p1 = __float_as_uint(br[2 * t + 1]); p2 = p0; }
-                            else w4_split_pair(br[2 * t], br[2 * t + 1], p0, p1, p2);
+                            else x3_split_pair(br[2 * t], br[2 * t + 1], p0, p1, p2);
                             bp[(g + 1) & 1][0][t] = p0; bp[(g + 1) & 1][1][t] = p1; bp[(g + 1) & 1][2][t] = p2;
                             if (t == 3 && g + 2 < 6) read_b8(g + 2, br);
                             __builtin_amdgcn_sched_barrier(0);

@@ -160,7 +160,6 @@ def conv_transpose2d(input, weight, bias=None, stride=1, padding=0, output_paddi
 UP2_TRANSPOSED = os.environ.get('PG_UP2_TRANSPOSED', '1') != '0'      # A/B: 0 = the transposed 3x3 stride-2 convolution as four phase launches
 
 UP2_TRANSPOSED_X3 = os.environ.get('PG_UP2_TRANSPOSED_X3', '1') != '0'
-_x3_of_pack = {}      # id(float32 pack) -> (weakref to it, its bf16 plane slabs)
 
 _pack_cache = {}      # (storage ptr, version, shape, strides, winograd, flip, transpose) -> (weakref to the source, packed weights)
 _PACK_CACHE_MAX_BYTES = 1 << 30
@@ -226,11 +225,7 @@ class _Conv2dMfma(torch.autograd.Function):
                 packs = dict(main=main)
                 if UP2_TRANSPOSED_X3 and cin % 16 == 0 and cin >= 32:
                     # ... with its main tiles on the bf16 pipe (csrc/conv2d_up2x3.h, float32-class): the split planes of the same pack, kept while the pack lives
-                    hit = _x3_of_pack.get(id(main))
-                    if hit is None or hit[0]() is not main:
-                        x3 = conv2d_mfma.pack_s2x3_planes(main, cout, cin)
-                        _x3_of_pack[id(main)] = hit = (weakref.ref(main, lambda r, k=id(main): _x3_of_pack.pop(k, None)), x3)
-                    packs['x3'] = hit[1]
+                    packs['x3'] = conv2d_mfma.pack_x3('up2', main, cout, cin)
                 y = conv2d_mfma.conv_up2_forward(x, packs, cout, x3=None if 'x3' in packs else False)
             else:
                 phases = conv2d_mfma.pack_transposed(weight, stride, padding, (h, w), out_hw)

@@ -80,6 +80,21 @@ def stop_timeline():
     return tl
 
 
+def timed_launch(tl):
+    """Start the timeline entry of one launch on `tl` (`_timeline` / `_wgrad_timeline`).  None -- no event, no work -- when no timeline is active (the normal path,
+    and the one inside hipGraph capture); else the start event is recorded and the returned `done(key, flops, nbytes)`, called after the launch, records the end
+    event and appends (key, flops, ev0, ev1, nbytes)."""
+    if tl is None:
+        return None
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+
+    def done(key, flops, nbytes):
+        ev1.record()
+        tl.append((key, flops, ev0, ev1, nbytes))
+    return done
+
+
 def _init(plugin_name='conv2d_plugin'):
     global _plugin
     if _plugin is None:
@@ -304,28 +319,32 @@ def pack_weight(w, scale=1.0, flip=False, transpose_oi=False, winograd=False):
 # The stride-2 3x3 convolution with padding 0 (after the FIR pass of a `down = 2` layer) on the bf16 matrix pipe (csrc/conv2d_s2x3.h: three-term operand splits,
 # float32-class).  PG_S2_X3=0 (read at every call, as PG_FIR_SHARED is): the fp32-MFMA kernel everywhere (A/B runs).
 S2_X3 = os.environ.get('PG_S2_X3', '1') != '0'
-_s2x3_of_pack = {}      # id(float32 pack) -> (weakref to it, its bf16 plane stream): made once per weight version, dropped with the pack
+_x3_planes = {}      # (id(float32 pack), kind) -> (weakref to the pack, its bf16 plane stream of that kind): made once per weight version, dropped with the pack
 
 
 def s2x3_wanted(n, cin, cout, h, w):
-    """Per-shape policy of the bf16-pipe stride-2 3x3 kernel: the shapes it serves (Cin % 16 == 0, Cin >= 32) minus those where tools/s2x3_probe.py measured it
-    slower than conv2d_mfma<3,3,2> (profiles/s2x3_probe.txt)."""
+    """Whether a stride-2 3x3 launch goes to the bf16-pipe kernel: every shape it serves (Cin % 16 == 0, Cin >= 32, H, W >= 3) unless PG_S2_X3=0 -- at import
+    or now (the variable is read at every call).  No shape is excluded."""
     if not S2_X3 or os.environ.get('PG_S2_X3', '1') == '0' or cin % 16 != 0 or cin < 32 or h < 3 or w < 3:
         return False
     return True
 
 
-def pack_s2x3(packed32, cout, cin):
-    """The bf16 plane stream of csrc/conv2d_s2x3.h from the float32 pack of a 3x3 kernel (`pack_weight`), cached for as long as that pack lives (the packs are
-    cached per weight version by their owners): [cout group of 128][16-channel chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16."""
-    hit = _s2x3_of_pack.get(id(packed32))
+def pack_x3(kind, packed32, cout, cin):
+    """The bf16 plane stream (csrc/bf16x3.h's three-term split) of a bf16-pipe kernel from the float32 pack of a 3x3 kernel (`pack_weight`), cached for as long
+    as that pack lives (the packs are cached per weight version by their owners).  `kind`:
+      'up2'  csrc/conv2d_up2x3.h  [m-block of 32 couts][16-channel chunk][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16 (what `pack_up2` stores under 'x3')
+      's2'   csrc/conv2d_s2x3.h   [cout group of 128][16-channel chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16"""
+    key = (id(packed32), kind)
+    hit = _x3_planes.get(key)
     if hit is not None and hit[0]() is packed32:
         return hit[1]
     lib = _init().lib
-    x3 = torch.empty([lib.pg_conv2d_s2x3_packed_size(cout, cin)], dtype=torch.uint8, device=packed32.device)
+    size, pack = {'up2': (lib.pg_conv2d_up2x3_packed_size, lib.pg_conv2d_up2x3_pack_weight), 's2': (lib.pg_conv2d_s2x3_packed_size, lib.pg_conv2d_s2x3_pack_weight)}[kind]
+    x3 = torch.empty([size(cout, cin)], dtype=torch.uint8, device=packed32.device)
     with torch.cuda.device(packed32.device):
-        nat.check(lib.pg_conv2d_s2x3_pack_weight(nat.ptr(packed32), nat.ptr(x3), cout, cin, nat.stream_of(packed32)), 'pg_conv2d_s2x3_pack_weight')
-    _s2x3_of_pack[id(packed32)] = (weakref.ref(packed32, lambda r, k=id(packed32): _s2x3_of_pack.pop(k, None)), x3)
+        nat.check(pack(nat.ptr(packed32), nat.ptr(x3), cout, cin, nat.stream_of(packed32)), f'pg_conv2d_{kind}x3_pack_weight')
+    _x3_planes[key] = (weakref.ref(packed32, lambda r, k=key: _x3_planes.pop(k, None)), x3)
     return x3
 
 
@@ -418,9 +437,7 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
         stats_part = torch.empty([n * cout * stats_T * 2], dtype=torch.float32, device=x.device)
         fz.stats_partial = stats_part.data_ptr()
     with torch.cuda.device(x.device):
-        if _timeline is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = timed_launch(_timeline)
         # the stride-2 3x3 layer without padding on the bf16 pipe (inference only: the training route keeps the fp32 kernel, as for conv2d_up2x3); a launch the
         # kernel declines (PG_ERR_UNSUPPORTED) goes to the fp32 kernel below
         s2x3 = (s2x3 is not False and not form and (kh, kw, int(stride)) == (3, 3, 2) and (int(pad_y), int(pad_x)) == (0, 0) and tuple(out_step) == (1, 1) and tuple(out_off) == (0, 0)
@@ -429,7 +446,7 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
                 and act in FUSED_ACTS and s2x3_wanted(n, cin, cout, h, w))
         st = -2
         if s2x3:
-            st = lib.pg_conv2d_s2x3_forward(nat.ptr(x), nat.ptr(pack_s2x3(packed, cout, cin)), nat.ptr(y), n, cin, h, w, cout, nat.i64arr(y.stride()), ctypes.byref(fz), nat.stream_of(x))
+            st = lib.pg_conv2d_s2x3_forward(nat.ptr(x), nat.ptr(pack_x3('s2', packed, cout, cin)), nat.ptr(y), n, cin, h, w, cout, nat.i64arr(y.stride()), ctypes.byref(fz), nat.stream_of(x))
             s2x3 = st != -2
         if s2x3:
             pass
@@ -451,10 +468,9 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
                 st = lib.pg_conv2d_forward(nat.ptr(x), nat.ptr(packed), nat.ptr(y), n, cin, h, w, cout, kh, kw, int(stride), int(pad_y), int(pad_x),
                                            int(oh), int(ow), nat.i64arr(y.stride()), int(out_step[0]), int(out_step[1]), int(out_off[0]), int(out_off[1]),
                                            ctypes.byref(fz), nat.stream_of(x))
-        if _timeline is not None:
-            ev1.record()
-            _timeline.append(((kh, kw, int(stride), label, f'N{n} {cin}->{cout} {h}x{w}' + (' spade' if spade is not None else '') + (' xf' if in_act != 'linear' else '') + (' mod' if in_scale is not None else '') + (' res' if residual is not None else '') + (' s2x3' if s2x3 else '')), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1,
-                              4 * (x.numel() + (x2.numel() if x2 is not None else 0) + n * ychan * oh * ow)))
+        if done:
+            done((kh, kw, int(stride), label, f'N{n} {cin}->{cout} {h}x{w}' + (' spade' if spade is not None else '') + (' xf' if in_act != 'linear' else '') + (' mod' if in_scale is not None else '') + (' res' if residual is not None else '') + (' s2x3' if s2x3 else '')), 2.0 * n * cout * oh * ow * cin * kh * kw,
+                 4 * (x.numel() + (x2.numel() if x2 is not None else 0) + n * ychan * oh * ow))
     nat.check(st, 'pg_conv2d_forward')
     if stats_part is not None:
         mean = torch.empty([n * cout], dtype=torch.float32, device=x.device)
@@ -604,20 +620,16 @@ def _weight_gradient_bf16x3(lib, x, dy, weight_shape, pad, stride, out_hw):
     d3 = torch.empty([3, n, oh, ow, cout], dtype=torch.bfloat16, device=x.device)
     dw = torch.empty([cout, cin, kh, kw], dtype=torch.float32, device=x.device)
     ws = torch.empty([splits * kh * kw * cout * cin], dtype=torch.float32, device=x.device)
-    tl = _wgrad_timeline
     with torch.cuda.device(x.device):
-        if tl is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = timed_launch(_wgrad_timeline)
         st = lib.pg_split3_bf16_cl(nat.ptr(x), nat.ptr(x3), n, cin, h * w, nat.stream_of(x))
         if st == 0:
             st = lib.pg_split3_bf16_cl(nat.ptr(dy), nat.ptr(d3), n, cout, oh * ow, nat.stream_of(x))
         if st == 0:
             st = lib.pg_conv2d16_wgrad_x3(nat.ptr(x3), nat.ptr(d3), nat.ptr(dw), nat.ptr(ws), n, cin, h, w, cout, kh, kw, stride, int(pad[0]), int(pad[1]), oh, ow, splits,
                                           nat.stream_of(x))
-        if tl is not None:
-            ev1.record()
-            tl.append(((kh, kw, stride, 'wgrad_bf16x3', f'N{n} {cin}->{cout} {h}x{w}'), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1, 4 * (x.numel() + dy.numel() + dw.numel())))
+        if done:
+            done((kh, kw, stride, 'wgrad_bf16x3', f'N{n} {cin}->{cout} {h}x{w}'), 2.0 * n * cout * oh * ow * cin * kh * kw, 4 * (x.numel() + dy.numel() + dw.numel()))
     if st == -2:
         return None
     nat.check(st, 'pg_conv2d16_wgrad_x3')
@@ -644,16 +656,12 @@ def weight_gradient(x, dy, weight_shape, pad, stride=1):
     x, dy = x.contiguous(), dy.contiguous()
     dw = torch.empty([cout, cin, kh, kw], dtype=torch.float32, device=x.device)
     ws = torch.empty([splits * kh * kw * cout * cin], dtype=torch.float32, device=x.device)
-    tl = _wgrad_timeline
     with torch.cuda.device(x.device):
-        if tl is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = timed_launch(_wgrad_timeline)
         st = lib.pg_conv2d_wgrad(nat.ptr(x), nat.ptr(dy), nat.ptr(dw), nat.ptr(ws), n, cin, h, w, cout, kh, kw, stride, int(pad[0]), int(pad[1]), oh, ow, splits,
                                  nat.stream_of(x))
-        if tl is not None:
-            ev1.record()
-            tl.append(((kh, kw, stride, 'wgrad', f'N{n} {cin}->{cout} {h}x{w}'), 2.0 * n * cout * oh * ow * cin * kh * kw, ev0, ev1, 4 * (x.numel() + dy.numel() + dw.numel())))
+        if done:
+            done((kh, kw, stride, 'wgrad', f'N{n} {cin}->{cout} {h}x{w}'), 2.0 * n * cout * oh * ow * cin * kh * kw, 4 * (x.numel() + dy.numel() + dw.numel()))
     nat.check(st, 'pg_conv2d_wgrad')
     return dw
 
@@ -666,21 +674,8 @@ def pack_up2(weight, flip=False, x3=True):
     packs = dict(main=pack_weight(w.contiguous()))
     cout, cin = int(w.shape[0]), int(w.shape[1])
     if x3 and UP2_X3 and cin % 16 == 0 and cin >= 32:     # round 6: the main tiles on the bf16 pipe (three-term operand splits, csrc/conv2d_up2x3.h): the split planes of the same pack, once per weight version
-        lib = _init().lib
-        x3 = torch.empty([lib.pg_conv2d_up2x3_packed_size(cout, cin)], dtype=torch.uint8, device=w.device)
-        with torch.cuda.device(w.device):
-            nat.check(lib.pg_conv2d_up2x3_pack_weight(nat.ptr(packs['main']), nat.ptr(x3), cout, cin, nat.stream_of(w)), 'pg_conv2d_up2x3_pack_weight')
-        packs['x3'] = x3
+        packs['x3'] = pack_x3('up2', packs['main'], cout, cin)
     return packs
-
-
-def pack_s2x3_planes(packed32, cout, cin):
-    """The bf16 plane slabs of `conv_up2_forward`'s bf16-pipe form from the float32 pack of a 3x3 kernel (`pack_weight`): what `pack_up2` stores under 'x3'."""
-    lib = _init().lib
-    x3 = torch.empty([lib.pg_conv2d_up2x3_packed_size(cout, cin)], dtype=torch.uint8, device=packed32.device)
-    with torch.cuda.device(packed32.device):
-        nat.check(lib.pg_conv2d_up2x3_pack_weight(nat.ptr(packed32), nat.ptr(x3), cout, cin, nat.stream_of(packed32)), 'pg_conv2d_up2x3_pack_weight')
-    return x3
 
 
 # PG_UP2_X3=0: the fp32-MFMA kernel everywhere (A/B runs).  Default: layers whose input is wider than 16 pixels (a multiple of 4) with Cin % 16 == 0 multiply on the bf16 pipe.
@@ -701,11 +696,8 @@ def conv_up2_forward(x, packs, cout, in_scale=None, out_scale=None, x3=None, edg
     y = buf[:, :, :, :ow]
     s_in = _f32c(in_scale, 'in_scale') if in_scale is not None else None
     s_out = _f32c(out_scale, 'out_scale') if out_scale is not None else None
-    tl = _timeline
     with torch.cuda.device(x.device):
-        if tl is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = timed_launch(_timeline)
         ksplit = lib.pg_conv2d_up2_splitk_plan(n, cin, h, w, cout)        # the 8^2 / 16^2 layers: shares of the input channels side by side, one summing pass
         # `x3` = False: the fp32-MFMA kernel whatever the pack holds (the training route: see training/networks.py _ModConvUp2Train)
         x3 = packs.get('x3') if (x3 is not False and UP2_X3 and ksplit == 1 and w > 16 and w % 4 == 0 and cin % 16 == 0 and cin >= 32 and x.data_ptr() % 16 == 0) else None
@@ -720,10 +712,9 @@ def conv_up2_forward(x, packs, cout, in_scale=None, out_scale=None, x3=None, edg
         else:
             st = lib.pg_conv2d_up2_forward(nat.ptr(x), nat.ptr(packs['main']), nat.ptr(y), n, cin, h, w, cout, nat.i64arr(y.stride()), nat.ptr(s_in), nat.ptr(s_out),
                                            nat.stream_of(x))
-        if tl is not None:
-            ev1.record()
-            tl.append(((3, 3, 2, 'direct', f'N{n} {cin}->{cout} {h}x{w} up2' + (' x3' if x3 is not None else '') + (' mod' if in_scale is not None else '')), 2.0 * n * cout * cin * 9 * h * w, ev0, ev1,
-                       4 * (x.numel() + n * cout * oh * ow)))
+        if done:
+            done((3, 3, 2, 'direct', f'N{n} {cin}->{cout} {h}x{w} up2' + (' x3' if x3 is not None else '') + (' mod' if in_scale is not None else '')), 2.0 * n * cout * cin * 9 * h * w,
+                 4 * (x.numel() + n * cout * oh * ow))
     nat.check(st, 'pg_conv2d_up2_forward')
     return y
 
@@ -760,15 +751,11 @@ def conv_stem7_forward(x, packed, cout, bias=None, act='linear', alpha=0.0, gain
     fz.act, fz.alpha, fz.gain = ACT_INDEX[act], float(alpha), float(gain)
     fz.clamp = -1.0 if clamp is None else float(clamp)
     fz.in_clamp, fz.in_gain = -1.0, 1.0
-    tl = _timeline
     with torch.cuda.device(x.device):
-        if tl is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = timed_launch(_timeline)
         st = lib.pg_conv2d_stem7x3_forward(nat.ptr(x), nat.ptr(packed), nat.ptr(y), n, h, w, cout, nat.i64arr(y.stride()), ctypes.byref(fz), nat.stream_of(x))
-        if tl is not None:
-            ev1.record()
-            tl.append(((7, 7, 1, 'direct', f'N{n} 3->{cout} {h}x{w} x3'), 2.0 * n * cout * h * w * 3 * 49, ev0, ev1, 4 * (x.numel() + y.numel())))
+        if done:
+            done((7, 7, 1, 'direct', f'N{n} 3->{cout} {h}x{w} x3'), 2.0 * n * cout * h * w * 3 * 49, 4 * (x.numel() + y.numel()))
     if st == -2:
         raise nat.NativeNotCovered('pg_conv2d_stem7x3_forward declined the launch')
     nat.check(st, 'pg_conv2d_stem7x3_forward')

@@ -314,11 +314,8 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
     args = [nat.ptr(x), nat.ptr(packed), nat.ptr(y), nat.PG_DTYPE[x.dtype], nat.PG_DTYPE[out_dtype], n, cin, h, w, cout_total, kh, kw, int(stride),
             int(pad_y), int(pad_x), oh, ow, int(sample_stride), nat.i64arr(y.stride()), int(out_step[0]), int(out_step[1]), int(out_off[0]), int(out_off[1]),
             ctypes.byref(fz)]
-    tl = conv2d_mfma._timeline
     with torch.cuda.device(x.device):
-        if tl is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = conv2d_mfma.timed_launch(conv2d_mfma._timeline)
         ksplit = 1
         if os.environ.get('PG_CONV_SPLITK', '1') != '0':
             ksplit = lib.pg_conv2d16_splitk_plan(n, cin, oh, ow, cout_total, kh, kw, int(stride))
@@ -327,11 +324,10 @@ def conv2d_forward(x, packed, cout, kh, kw, stride=1, pad=(0, 0), out_hw=None, y
             st = lib.pg_conv2d16_forward_splitk(*args, nat.ptr(ws), ksplit, nat.stream_of(x))
         else:
             st = lib.pg_conv2d16_forward(*args, nat.stream_of(x))
-        if tl is not None:
-            ev1.record()
-            tl.append(((kh, kw, int(stride), 'mfma16', f'N{n} {cin}->{cout_total}{" (4 phases)" if phases else ""} {h}x{w} {str(x.dtype)[6:]}'), 2.0 * n * cout_total * oh * ow * cin * kh * kw, ev0, ev1,
-                       x.element_size() * (x.numel() + n * cout_total * oh * ow) + (y.element_size() - x.element_size()) * n * cout_total * oh * ow
-                       + packed.numel() * packed.element_size()))       # algorithmic bytes: x + y + the packed weights this launch reads
+        if done:
+            done((kh, kw, int(stride), 'mfma16', f'N{n} {cin}->{cout_total}{" (4 phases)" if phases else ""} {h}x{w} {str(x.dtype)[6:]}'), 2.0 * n * cout_total * oh * ow * cin * kh * kw,
+                 x.element_size() * (x.numel() + n * cout_total * oh * ow) + (y.element_size() - x.element_size()) * n * cout_total * oh * ow
+                 + packed.numel() * packed.element_size())       # algorithmic bytes: x + y + the packed weights this launch reads
     nat.check(st, 'pg_conv2d16_forward')
     return y
 
@@ -374,19 +370,15 @@ def conv_up2_fused(x, packed, cout, fir_x, sample_stride=0, out_scale=None, nois
     fz.clamp = -1.0 if clamp is None else float(clamp)
     fz.phase_cout = cout
     taps = (ctypes.c_float * 4)(*[float(v) for v in fir_x])
-    tl = conv2d_mfma._timeline
     with torch.cuda.device(x.device):
-        if tl is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+        done = conv2d_mfma.timed_launch(conv2d_mfma._timeline)
         st = lib.pg_conv2d16_up2_fused(nat.ptr(x), nat.ptr(packed), nat.ptr(y), nat.PG_DTYPE[x.dtype], n, cin, h, w, cout, int(sample_stride),
                                        nat.i64arr(y.stride()), taps, ctypes.byref(fz), nat.stream_of(x))
-        if tl is not None:
-            ev1.record()
+        if done:
             # executed flops: 18 tap-products per position and (cin, cout) pair (the launch's tiles overlap by 2 of 32 columns on top of that);
             # SURVEY 8d counts the transposed convolution as 2 * N * Cin * Hin * Win * Cout * 9: `honest_flops`
-            tl.append(((3, 3, 1, 'mfma16', f'N{n} {cin}->{cout} (up2 fused-x) {h}x{w} {str(x.dtype)[6:]}'), 2.0 * n * cout * h * w * cin * 18, ev0, ev1,
-                       x.element_size() * (x.numel() + y.numel()) + packed.numel() * packed.element_size()))
+            done((3, 3, 1, 'mfma16', f'N{n} {cin}->{cout} (up2 fused-x) {h}x{w} {str(x.dtype)[6:]}'), 2.0 * n * cout * h * w * cin * 18,
+                 x.element_size() * (x.numel() + y.numel()) + packed.numel() * packed.element_size())
     nat.check(st, 'pg_conv2d16_up2_fused')
     return y
 

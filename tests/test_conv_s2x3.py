@@ -134,8 +134,8 @@ def test_packed_planes_add_up_to_the_scaled_weight(cout, cin):
     wt = torch.randn([cout, cin, 3, 3], generator=gen)
     scale = 0.37
     packed = conv2d_mfma.pack_weight(wt.to(DEV), scale=scale)
-    x3 = conv2d_mfma.pack_s2x3(packed, cout, cin)
-    assert conv2d_mfma.pack_s2x3(packed, cout, cin) is x3                                    # once per pack
+    x3 = conv2d_mfma.pack_x3('s2', packed, cout, cin)
+    assert conv2d_mfma.pack_x3('s2', packed, cout, cin) is x3                                    # once per pack
     groups, nchunks = (cout + 127) // 128, cin // 16
     assert x3.numel() == conv2d_mfma._init().lib.pg_conv2d_s2x3_packed_size(cout, cin) == groups * nchunks * 4 * 27 * 1024
     bits = x3.cpu().view(torch.int16).to(torch.int32).reshape(groups, nchunks, 4, 9, 3, 2, 32, 8)
@@ -145,6 +145,87 @@ def test_packed_planes_add_up_to_the_scaled_weight(cout, cin):
     want = wt * torch.tensor(scale, dtype=torch.float32)
     assert torch.equal(got[:cout], want)
     assert not got[cout:].any()
+
+
+def _readd(x3, *shape):
+    """A bf16 plane stream as float32 values of `shape` (the plane axis among them)."""
+    return (x3.cpu().view(torch.int16).to(torch.int32).reshape(*shape) << 16).view(torch.float32)
+
+
+@pytest.mark.parametrize('cout,cin', [(40, 48), (96, 32)])
+def test_up2_packed_planes_add_up_to_the_scaled_weight(cout, cin):
+    """pack_x3('up2'): [m-block of 32][chunk][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16 (csrc/conv2d_up2x3.h); the three planes, re-added in float32
+    on the host, are w * scale bit for bit, and zero beyond Cout."""
+    from torch_utils.ops import conv2d_mfma
+    gen = torch.Generator().manual_seed(2 * cout + cin)
+    wt = torch.randn([cout, cin, 3, 3], generator=gen)
+    scale = 0.37
+    packed = conv2d_mfma.pack_weight(wt.to(DEV), scale=scale)
+    x3 = conv2d_mfma.pack_x3('up2', packed, cout, cin)
+    mblocks, nchunks = (cout + 31) // 32, cin // 16
+    assert x3.numel() == conv2d_mfma._init().lib.pg_conv2d_up2x3_packed_size(cout, cin) == mblocks * nchunks * 27 * 1024
+    planes = _readd(x3, mblocks, nchunks, 9, 3, 2, 32, 8)
+    total = (planes[:, :, :, 0] + planes[:, :, :, 1]) + planes[:, :, :, 2]                    # [m-block, chunk, tap, k-half, cout 32, channel 8]
+    got = total.permute(0, 4, 1, 3, 5, 2).reshape(mblocks * 32, cin, 3, 3)                   # [cout, (chunk, k-half, channel), tap]
+    want = wt * torch.tensor(scale, dtype=torch.float32)
+    assert torch.equal(got[:cout], want)
+    assert not got[cout:].any()
+
+
+@pytest.mark.parametrize('flip', [False, True])
+@pytest.mark.parametrize('cout', [40, 96])
+def test_stem7_packed_planes_add_up_to_the_scaled_weight(cout, flip):
+    """pack_stem7: [m-tile of 32 couts][K step 11][plane 3][lane 64][8] bf16 with lane = (K step half, cout & 31), K group g = 2 step + half = 3 kx + ci, the 8
+    values of a lane = ky 0..6 and one zero (csrc/conv2d_stem7x3.h).  The planes re-add to w * scale (flipped when asked) bit for bit; every slot the window does
+    not use -- group >= 21, row 7, cout >= Cout -- is zero."""
+    from torch_utils.ops import conv2d_mfma
+    gen = torch.Generator().manual_seed(cout + int(flip))
+    wt = torch.randn([cout, 3, 7, 7], generator=gen)
+    scale = 0.37
+    x3 = conv2d_mfma.pack_stem7(wt.to(DEV), scale=scale, flip=flip)
+    mtiles = (cout + 63) // 64 * 2
+    assert x3.numel() == conv2d_mfma._init().lib.pg_conv2d_stem7x3_packed_size(cout) == mtiles * 11 * 3 * 1024
+    planes = _readd(x3, mtiles, 11, 3, 2, 32, 8)                                             # [m-tile, step, plane, half, cout 32, row 8]
+    total = (planes[:, :, 0] + planes[:, :, 1]) + planes[:, :, 2]
+    slots = total.permute(0, 3, 1, 2, 4).reshape(mtiles * 32, 22, 8)                         # [cout, group, row]
+    got = slots[:, :21, :7].reshape(mtiles * 32, 7, 3, 7).permute(0, 2, 3, 1)                # [cout, (kx, ci), ky] -> [cout, ci, ky, kx]
+    want = (wt.flip([2, 3]) if flip else wt) * torch.tensor(scale, dtype=torch.float32)
+    assert torch.equal(got[:cout], want)
+    assert not slots[cout:].any() and not slots[:, 21].any() and not slots[:, :, 7].any()
+
+
+def test_split3_planes_add_up_and_keep_an_infinite_value():
+    """pg_split3_bf16_cl (the guarded split of csrc/bf16x3.h) on a ragged pixel tile and a ragged channel tile: the three channels-last planes re-add to x bit for
+    bit where x is finite; an infinite element keeps +-inf in the leading plane with both remainders zero."""
+    from torch_utils.ops import conv2d_mfma
+    from torch_utils.ops import _native as nat
+    n, c, hw = 2, 24, 37
+    x = torch.randn([n, c, hw], generator=torch.Generator().manual_seed(37)) * 100
+    x[0, 3, 5], x[1, 17, 36] = float('inf'), float('-inf')
+    xd = x.to(DEV)
+    out = torch.empty([3, n, hw, c], dtype=torch.bfloat16, device=DEV)
+    nat.check(conv2d_mfma._init().lib.pg_split3_bf16_cl(nat.ptr(xd), nat.ptr(out), n, c, hw, nat.stream_of(xd)), 'pg_split3_bf16_cl')
+    planes = out.cpu().float().permute(0, 1, 3, 2)                                           # [3, N, C, HW]
+    fin = torch.isfinite(x)
+    assert int((~fin).sum()) == 2
+    total = (planes[0] + planes[1]) + planes[2]
+    assert torch.equal(total[fin], x[fin])
+    assert torch.equal(planes[0][~fin], x[~fin])
+    assert not planes[1][~fin].any() and not planes[2][~fin].any()
+
+
+def test_pack_x3_is_cached_per_pack_and_kind():
+    """One plane stream per (float32 pack, kind) for as long as the pack lives; the table's entries go with the pack."""
+    import gc
+    from torch_utils.ops import conv2d_mfma
+    p = conv2d_mfma.pack_weight(torch.randn([40, 32, 3, 3], generator=torch.Generator().manual_seed(1)).to(DEV))
+    up2, s2 = conv2d_mfma.pack_x3('up2', p, 40, 32), conv2d_mfma.pack_x3('s2', p, 40, 32)
+    assert conv2d_mfma.pack_x3('up2', p, 40, 32) is up2 and conv2d_mfma.pack_x3('s2', p, 40, 32) is s2 and up2 is not s2
+    ident = id(p)
+    assert {(ident, 'up2'), (ident, 's2')} <= set(conv2d_mfma._x3_planes)
+    del p
+    gc.collect()
+    assert not [k for k in conv2d_mfma._x3_planes if k[0] == ident]
 
 
 @pytest.mark.parametrize('h,w', [(64, 64), (37, 51)])

@@ -45,9 +45,9 @@ for (N, cin, cout, H) in [(8, 64, 128, 513), (8, 128, 256, 257)]:
     packs, last = {}, {}
     for v in VARIANTS:
         conv2d_mfma._plugin = libs[v]
-        conv2d_mfma._s2x3_of_pack.clear()
+        conv2d_mfma._x3_planes.clear()
         packs[v] = conv2d_mfma.pack_weight(w)
-        conv2d_mfma.pack_s2x3(packs[v], cout, cin)
+        conv2d_mfma.pack_x3('s2', packs[v], cout, cin)
     for r in range(6):
         for v in VARIANTS:
             conv2d_mfma._plugin = libs[v]
