@@ -12,7 +12,7 @@
  *                           pg_conv1x1_small16;  glue: pg_modconv_{dcoefs,w2,prep}, pg_instance_norm_stats, pg_spade_*
  *   patch_routing_plugin.so pg_warp_perspective_u8, pg_patch_compose_u8[_k], pg_patch_compose_ordered_u8[_k]
  *   augment_plugin.so       pg_augment_warp, pg_augment_warp_adjoint, pg_augment_color, pg_augment_late
- *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8
+ *   tryon_plugin.so         pg_tryon_row_extent_u8, pg_tryon_inputs, pg_tryon_triptych_u8, pg_tryon_panels_u8
  *   train_fetch_plugin.so   pg_train_fetch
  *   tryon_front_plugin.so   pg_tryon_front_stats, pg_tryon_front_bit_rows, pg_tryon_front_compose
  *   vgg_loss_plugin.so      pg_maxpool2x2, pg_maxpool2x2_backward, pg_l1_pair_blocks, pg_l1_pair_sum, pg_l1_pair_grad
@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 20
+#define PG_ABI_VERSION 21
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -693,10 +693,15 @@ int pg_augment_abi_version(void);
  *   bound_rows[i, y] after the mode's post-routing rule: PG_TRYON_UPPER zeroes the rows above extents[i, 1] (the last row of
  *   denorm_upper_img_wo_sleeve); PG_TRYON_FULL adds 255 (mod 256) from row extents[i, 0] on (the routed lower garment's first row) and zeroes the plane
  *   when label[i] == 2 (a dress); PG_TRYON_LOWER takes the rows as they are (extents may be NULL).  An extent of -1 leaves the rows unchanged.
+ *   PG_TRYON_OUTFIT (the top of one clothes image, the lower garment of another: not one of the reference's modes) takes PG_TRYON_FULL's rule.
  * pg_tryon_triptych_u8: finetune_img float32 [n, 3, H, W] + clothes, image uint8 [n, H, W, 3] -> out uint8 [n, H, 3 cw, 3]: columns x0 : x0 + cw of
  *   clothes | person | result.  result = clip((x + 1) * 127.5, 0, 255) truncated, NaN -> 0; clothes / person = ((u / 127.5 - 1) + 1) * 127.5 truncated
- *   (the reference's round trip, unclipped: it can be one below u).  x0, cw, W multiples of 4. */
-enum pg_tryon_mode { PG_TRYON_UPPER = 0, PG_TRYON_LOWER = 1, PG_TRYON_FULL = 2 };
+ *   (the reference's round trip, unclipped: it can be one below u).  x0, cw, W multiples of 4.
+ * pg_tryon_panels_u8: the same packing for k source images (1 <= k <= PG_TRYON_MAX_PANEL_SOURCES; `sources` is a HOST array of k device pointers, each
+ *   uint8 [n, H, W, 3]) -> out uint8 [n, H, (k + 1) cw, 3]: columns x0 : x0 + cw of source 0 | ... | source k-1 | result, every panel with the triptych's
+ *   arithmetic.  The outfit mode packs upper clothes | lower clothes | person | result (k = 3); k = 2 is pg_tryon_triptych_u8. */
+enum pg_tryon_mode { PG_TRYON_UPPER = 0, PG_TRYON_LOWER = 1, PG_TRYON_FULL = 2, PG_TRYON_OUTFIT = 3 };
+#define PG_TRYON_MAX_PANEL_SOURCES 3
 typedef struct pg_tryon_io {
     const unsigned char* image;            /* [n, H, W, 3] */
     const unsigned char* pose;             /* [n, H, W, 3] */
@@ -721,6 +726,8 @@ int pg_tryon_row_extent_u8(const unsigned char* canvases, int ncanvases, int h, 
 int pg_tryon_inputs(const pg_tryon_io* io, int n, int H, int W, int h, int w, int mode, void* stream);
 int pg_tryon_triptych_u8(const float* finetune_img, const unsigned char* clothes, const unsigned char* image, unsigned char* out, int n, int H, int W,
                          int x0, int cw, void* stream);
+int pg_tryon_panels_u8(const float* finetune_img, const unsigned char* const* sources, int k, unsigned char* out, int n, int H, int W, int x0, int cw,
+                       void* stream);
 int pg_tryon_abi_version(void);
 
 /* train_fetch_plugin.so -- the data fetch of the training loop (training/train_fetch.py; reference training_loop_fullbody.py:549-601 and the tail of
@@ -767,15 +774,21 @@ int pg_train_fetch_abi_version(void);
  * Three launches per batch, in this order on one stream, none of which reads anything back:
  * pg_tryon_front_stats: zeroes stats (a memset node) and fills, per sample, PG_FRONT_STATS int32: the pixel counts of the label groups {5,7} {6} {9}
  *   {12} of person_parsing [0..3] and clothes_parsing [4..7], H - (first row) of each group (0 = absent) [8..15], and the 3 x 256 histogram of the
- *   person's image bytes under labels {10,13} [16..783] (bin 0 is not read: the skin medians ignore zero bytes).
+ *   person's image bytes under labels {10,13} [16..783] (bin 0 is not read: the skin medians ignore zero bytes), and, when lower_src_parsing != NULL,
+ *   the pixel counts of its four label groups [784..787] (0 otherwise).  No mode argument: the pointer's presence switches the count.
  * pg_tryon_front_bit_rows: bit_rows [n, 5, H, (H + 31) / 32] uint32, bit x % 32 of word x / 32 = pixel x: planes 0..3 the four arm bands (the
  *   quadrilateral bands[i, b] dilated along x by 35 (upper arm) or 28 (fore-arm); b = 2 * arm + (0 upper arm, 1 fore-arm), arm 0 = label 14), plane 4 the mode's
  *   canvas mask eroded along x (taps -4..+3, taps outside the frame ignored).  Reads stats (the canvas mask depends on the garment classes).
  * pg_tryon_front_compose: resolves the per-sample decisions from stats (garment classes, dress rules, label, bound, the skin medians) and writes every
  *   map of a ``collate_unrouted`` batch; finishes the dilation / erosion along y.  sleeve is written iff garment_parsing != NULL; canvas is not
- *   written in PG_TRYON_FULL.
+ *   written in PG_TRYON_FULL and PG_TRYON_OUTFIT.
+ * PG_TRYON_OUTFIT is PG_TRYON_FULL with the lower garment cut from a second clothes source: lower_img / lower_mask come from lower_src_img under the
+ *   garment classes of lower_src_parsing; label = 0 if that parsing has pants, else 1 if it has a skirt, else 2 if clothes_parsing has a dress, else 1
+ *   (nothing is zeroed for a dress); lower_clothes = lower_src_img padded like clothes; bit_rows writes no canvas plane.  The mode needs both lower
+ *   sources (bit_rows, compose) and lower_clothes (compose), and lower_clothes must be NULL in every other mode: PG_ERR_INVALID_ARG otherwise, before
+ *   anything is launched.
  * H % 4 == 0, H <= 4096, 0 <= left, left + W <= H; pointers 4-byte aligned (PG_ERR_UNSUPPORTED otherwise). */
-#define PG_FRONT_STATS 784
+#define PG_FRONT_STATS 788
 #define PG_FRONT_PRIMS 37                  /* rows of the pose table: 19 limbs + 18 joints */
 typedef struct pg_front_io {
     const unsigned char* person_img;       /* [n, H, W, 3] as decoded */
@@ -799,10 +812,14 @@ typedef struct pg_front_io {
     unsigned char* clothes;                /* [n, H, H, 3] */
     unsigned char* pose;                   /* [n, H, H, 3] */
     unsigned char* retain_mask;            /* [n, H, H, 1] */
-    unsigned char* canvas;                 /* [n, H, H, 3] or NULL (PG_TRYON_FULL) */
+    unsigned char* canvas;                 /* [n, H, H, 3] or NULL (PG_TRYON_FULL, PG_TRYON_OUTFIT) */
     unsigned char* bound;                  /* [n, H] */
     float* skin;                           /* [n, 3] */
     int* label;                            /* [n] */
+    /* PG_TRYON_OUTFIT (appended: a caller that fills the fields above by name leaves these NULL) */
+    const unsigned char* lower_src_img;    /* [n, H, W, 3] as decoded: the lower clothes, or NULL */
+    const unsigned char* lower_src_parsing;/* [n, H, W] or NULL */
+    unsigned char* lower_clothes;          /* [n, H, H, 3] or NULL */
 } pg_front_io;
 int pg_tryon_front_stats(const pg_front_io* io, int n, int H, int W, void* stream);
 int pg_tryon_front_bit_rows(const pg_front_io* io, int n, int H, int W, int left, int mode, void* stream);

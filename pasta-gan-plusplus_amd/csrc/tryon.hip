@@ -2,6 +2,7 @@
 //   pg_tryon_row_extent_u8  first / last non-zero row of every canvas of a batch (the two post-routing bound rules)
 //   pg_tryon_inputs         the seven float32 NCHW generator inputs of training.dataset.to_generator_inputs, from uint8 NHWC sources, in one launch
 //   pg_tryon_triptych_u8    clothes | person | result, columns x0 : x0 + cw of each, as uint8 RGB rows (test.py:162-181)
+//   pg_tryon_panels_u8      the same packing for k source images: source 0 | ... | source k-1 | result (the outfit mode's four panels)
 // The results equal torch on the GPU bit for bit: every value is built with the float32 operations torch runs, in its order, and nothing is
 // contracted into a fused multiply-add (the pragma below).  torch divides a GPU tensor by the Python scalar 127.5 by multiplying with the rounded
 // reciprocal 1.0f / 127.5f (tests/test_tryon_gpu.py pins this over all 256 byte values), so `unit` does the same.
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void inputs_kernel(pg_tryon_io io, int H, int 
         uint32_t b = io.bound_rows[(int64_t)n * H + y];
         if (mode == PG_TRYON_UPPER) {                                // bound[0:ymax] *= 0, ymax = last row of denorm_upper_img_wo_sleeve
             if (s_hi >= 0 && y < s_hi) b = 0;
-        } else if (mode == PG_TRYON_FULL) {                          // bound[ymin:] += 255 from the routed lower garment; a dress: bound * 0
+        } else if (mode == PG_TRYON_FULL || mode == PG_TRYON_OUTFIT) {       // bound[ymin:] += 255 from the routed lower garment; a dress: bound * 0
             if (s_lbl == 2) b = 0;
             else if (s_lo >= 0 && y >= s_lo) b = (b + 255u) & 0xffu;
         }
@@ -158,18 +159,26 @@ __device__ __forceinline__ uint32_t result_byte(float x) {
     return (uint32_t)(int)v;
 }
 
-__global__ __launch_bounds__(256) void triptych_u8_kernel(const float* __restrict__ fin, const uint8_t* __restrict__ clothes, const uint8_t* __restrict__ image,
-                                                          uint8_t* __restrict__ out, int n_rows, int H, int W, int x0, int cw) {
-    const int qpr = 3 * cw / 4;                                      // quads per output row
+// One kernel body for both packers: K source panels (the triptych: clothes, person; the outfit panels: upper clothes, lower clothes, person), then the
+// result.  K is a compile-time constant: the triptych's instance is the kernel it always was.
+template <int K> struct PanelSources { const uint8_t* src[K]; };
+
+template <int K>
+__global__ __launch_bounds__(256) void panels_u8_kernel(const float* __restrict__ fin, PanelSources<K> srcs, uint8_t* __restrict__ out, int n_rows, int H,
+                                                        int W, int x0, int cw) {
+    const int qpr = (K + 1) * cw / 4;                                // quads per output row
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= (int64_t)n_rows * qpr) return;
     const int row = (int)(q / qpr), xq = (int)(q - (int64_t)row * qpr) * 4;     // output column of the quad's first pixel
     const int n = row / H, y = row - n * H;
-    const int part = xq / cw, x = x0 + xq - part * cw;              // 0 clothes, 1 person, 2 result (cw % 4 == 0: a quad stays in one part)
+    const int part = xq / cw, x = x0 + xq - part * cw;              // 0 .. K-1 the sources, K the result (cw % 4 == 0: a quad stays in one part)
     uint32_t o[3] = {0u, 0u, 0u};
-    if (part < 2) {
+    if (part < K) {
         uint32_t w[3];
-        load_px4<3>((part == 0 ? clothes : image) + (((int64_t)n * H + y) * W + x) * 3, w);
+        const uint8_t* s = srcs.src[0];                              // (selected without indexing the kernel argument by a run-time value)
+#pragma unroll
+        for (int i = 1; i < K; i++) s = part == i ? srcs.src[i] : s;
+        load_px4<3>(s + (((int64_t)n * H + y) * W + x) * 3, w);
 #pragma unroll
         for (int i = 0; i < 12; i++) o[i >> 2] |= source_byte(byte_of(w, i)) << ((i & 3) * 8);
     } else {
@@ -186,9 +195,17 @@ __global__ __launch_bounds__(256) void triptych_u8_kernel(const float* __restric
             }
         }
     }
-    uint32_t* d = reinterpret_cast<uint32_t*>(out + ((int64_t)row * 3 * cw + xq) * 3);
+    uint32_t* d = reinterpret_cast<uint32_t*>(out + ((int64_t)row * (K + 1) * cw + xq) * 3);
 #pragma unroll
     for (int i = 0; i < 3; i++) __builtin_nontemporal_store(o[i], d + i);
+}
+
+template <int K>
+void launch_panels(const float* fin, const unsigned char* const* sources, unsigned char* out, int n, int H, int W, int x0, int cw, int64_t quads,
+                   hipStream_t stream) {
+    PanelSources<K> srcs;
+    for (int i = 0; i < K; i++) srcs.src[i] = sources[i];
+    hipLaunchKernelGGL(panels_u8_kernel<K>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, fin, srcs, out, n * H, H, W, x0, cw);
 }
 
 }  // namespace
@@ -205,7 +222,7 @@ PG_EXPORT int pg_tryon_row_extent_u8(const unsigned char* canvases, int ncanvase
 
 PG_EXPORT int pg_tryon_inputs(const pg_tryon_io* io, int n, int H, int W, int h, int w, int mode, void* stream) {
     if (!io || n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return PG_ERR_INVALID_ARG;
-    if (mode != PG_TRYON_UPPER && mode != PG_TRYON_LOWER && mode != PG_TRYON_FULL) return PG_ERR_INVALID_ARG;
+    if (mode != PG_TRYON_UPPER && mode != PG_TRYON_LOWER && mode != PG_TRYON_FULL && mode != PG_TRYON_OUTFIT) return PG_ERR_INVALID_ARG;
     const void* req[] = {io->image, io->pose, io->retain_mask, io->denorm_upper, io->denorm_lower, io->norm_img, io->norm_img_lower, io->skin, io->label,
                          io->bound_rows, io->c, io->retain, io->pose_out, io->denorm_upper_out, io->denorm_lower_out, io->upper_mask_out, io->lower_mask_out};
     for (const void* p : req)
@@ -224,15 +241,26 @@ PG_EXPORT int pg_tryon_inputs(const pg_tryon_io* io, int n, int H, int W, int h,
     return pg::launch_status();
 }
 
+PG_EXPORT int pg_tryon_panels_u8(const float* finetune_img, const unsigned char* const* sources, int k, unsigned char* out, int n, int H, int W, int x0,
+                                 int cw, void* stream) {
+    if (!finetune_img || !sources || !out || k < 1 || k > PG_TRYON_MAX_PANEL_SOURCES || n <= 0 || H <= 0 || W <= 0 || cw <= 0 || x0 < 0 || x0 + cw > W)
+        return PG_ERR_INVALID_ARG;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(out);
+    for (int i = 0; i < k; i++) {
+        if (!sources[i]) return PG_ERR_INVALID_ARG;
+        bits |= reinterpret_cast<uintptr_t>(sources[i]);
+    }
+    if (x0 % 4 || cw % 4 || W % 4 || !pg::aligned16(finetune_img) || (bits & 3u)) return PG_ERR_UNSUPPORTED;
+    const int64_t quads = (int64_t)n * H * ((k + 1) * cw / 4);
+    if (quads / 256 + 1 > 0x7fffffffLL || (int64_t)H * W > 0x3fffffffLL || (int64_t)n * H > 0x7fffffffLL) return PG_ERR_TOO_LARGE;
+    if (k == 1) launch_panels<1>(finetune_img, sources, out, n, H, W, x0, cw, quads, (hipStream_t)stream);
+    else if (k == 2) launch_panels<2>(finetune_img, sources, out, n, H, W, x0, cw, quads, (hipStream_t)stream);
+    else launch_panels<3>(finetune_img, sources, out, n, H, W, x0, cw, quads, (hipStream_t)stream);
+    return pg::launch_status();
+}
+
 PG_EXPORT int pg_tryon_triptych_u8(const float* finetune_img, const unsigned char* clothes, const unsigned char* image, unsigned char* out, int n, int H,
                                    int W, int x0, int cw, void* stream) {
-    if (!finetune_img || !clothes || !image || !out || n <= 0 || H <= 0 || W <= 0 || cw <= 0 || x0 < 0 || x0 + cw > W) return PG_ERR_INVALID_ARG;
-    if (x0 % 4 || cw % 4 || W % 4 || !pg::aligned16(finetune_img) || (reinterpret_cast<uintptr_t>(clothes) | reinterpret_cast<uintptr_t>(image) |
-                                                                       reinterpret_cast<uintptr_t>(out)) & 3u)
-        return PG_ERR_UNSUPPORTED;
-    const int64_t quads = (int64_t)n * H * (3 * cw / 4);
-    if (quads / 256 + 1 > 0x7fffffffLL || (int64_t)H * W > 0x3fffffffLL) return PG_ERR_TOO_LARGE;
-    hipLaunchKernelGGL(triptych_u8_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, finetune_img, clothes, image, out, n * H,
-                       H, W, x0, cw);
-    return pg::launch_status();
+    const unsigned char* sources[2] = {clothes, image};
+    return pg_tryon_panels_u8(finetune_img, sources, 2, out, n, H, W, x0, cw, stream);
 }

@@ -7,6 +7,8 @@
 // are integer arithmetic); square dilation and the 8 x 8 erosion as a pass along x (bit rows) and a pass along y (compose); images pad with 255,
 // everything else with 0.  Only the pose primitives are culled by bounding box (a segment reaches 2.5 pixels, a disc less than 5: the boxes grow by 3 and
 // 5); a quadrilateral is tested at every pixel, because a degenerate one (a limb of zero length) covers the whole frame under `_Raster.quad`'s rule.
+// PG_TRYON_OUTFIT is PG_TRYON_FULL with the lower garment cut from a second clothes source (lower_src_img / lower_src_parsing): the statistics count that
+// source's label groups too, compose reads it through the same padded-frame loads as the clothes source and writes it out padded (lower_clothes).
 // Memory-bound streams: one lane = 4 consecutive pixels of a row, the uint8 sides move as dwords (byte loads where W or left is no multiple of 4).
 #include "pg_common.h"
 #include "pg_stage.h"
@@ -19,6 +21,7 @@ namespace {
 using namespace pg::stage;       // byte_of, load_px4
 
 constexpr int kStats = PG_FRONT_STATS, kPrims = PG_FRONT_PRIMS;
+constexpr int kLowerCnt = 784;                           // stats[784..787]: the label-group counts of the lower clothes' parsing (outfit mode)
 constexpr int kStatRows = 32;                            // rows per workgroup of the statistics kernel (a multiple of 4: its dwords stay aligned)
 constexpr int kBandK[2] = {35, 28};                      // dilation of the upper-arm / fore-arm band (dataset.py BAND_K)
 enum { TOPS = 0, DRESSES = 1, PANTS = 2, SKIRT = 3 };    // garment classes, and the label groups {5,7} {6} {9} {12} that start in them
@@ -27,22 +30,36 @@ __device__ __forceinline__ int group_of(uint32_t label) {
     return (label == 5u || label == 7u) ? 0 : label == 6u ? 1 : label == 9u ? 2 : label == 12u ? 3 : -1;
 }
 
+__host__ __device__ __forceinline__ bool no_canvas(int mode) { return mode == PG_TRYON_FULL || mode == PG_TRYON_OUTFIT; }
+
 // ----------------------------------------------------------------------------------------------------------- statistics
 // Grid: x = blocks of kStatRows rows of the W-wide sources, y = sample.  stats was zeroed by the entry point's memset node.
 __global__ __launch_bounds__(256) void front_stats_kernel(pg_front_io io, int H, int W) {
     const int n = blockIdx.y;
-    __shared__ int s_cnt[8], s_key[8], s_hist[768];
+    __shared__ int s_cnt[8], s_key[8], s_lcnt[4], s_hist[768];
     for (int i = threadIdx.x; i < 768; i += 256) s_hist[i] = 0;
     if (threadIdx.x < 8) { s_cnt[threadIdx.x] = 0; s_key[threadIdx.x] = 0; }
+    if (threadIdx.x < 4) s_lcnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t P = (int64_t)H * W;                                        // H % 4 == 0: every sample starts on a dword
     const int y0 = blockIdx.x * kStatRows, y1 = y0 + kStatRows < H ? y0 + kStatRows : H;
     const uint32_t* pp = reinterpret_cast<const uint32_t*>(io.person_parsing + n * P);
     const uint32_t* cp = reinterpret_cast<const uint32_t*>(io.clothes_parsing + n * P);
+    const uint32_t* lp4 = io.lower_src_parsing ? reinterpret_cast<const uint32_t*>(io.lower_src_parsing + n * P) : nullptr;      // (uniform)
     const uint8_t* img = io.person_img + n * P * 3;
-    int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, key[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lcnt[4] = {0, 0, 0, 0};
     for (int64_t i = (int64_t)y0 * W / 4 + threadIdx.x; i < (int64_t)y1 * W / 4; i += 256) {
         const uint32_t pw = __builtin_nontemporal_load(pp + i), cw = __builtin_nontemporal_load(cp + i);
+        if (lp4) {                                                           // the lower clothes' label groups: counts only (no rule reads their rows)
+            const uint32_t lw = __builtin_nontemporal_load(lp4 + i);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int gl = group_of((lw >> (8 * k)) & 0xffu);
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                    if (gl == g) lcnt[g]++;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int64_t px = i * 4 + k;
@@ -68,12 +85,16 @@ __global__ __launch_bounds__(256) void front_stats_kernel(pg_front_io io, int H,
         if (cnt[j]) atomicAdd(&s_cnt[j], cnt[j]);
         if (key[j]) atomicMax(&s_key[j], key[j]);
     }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (lcnt[j]) atomicAdd(&s_lcnt[j], lcnt[j]);
     __syncthreads();
     int* st = io.stats + (int64_t)n * kStats;
     if (threadIdx.x < 8) {
         if (s_cnt[threadIdx.x]) atomicAdd(st + threadIdx.x, s_cnt[threadIdx.x]);
         if (s_key[threadIdx.x]) atomicMax(st + 8 + threadIdx.x, s_key[threadIdx.x]);
     }
+    if (threadIdx.x < 4 && s_lcnt[threadIdx.x]) atomicAdd(st + kLowerCnt + threadIdx.x, s_lcnt[threadIdx.x]);
     for (int i = threadIdx.x; i < 768; i += 256)
         if (s_hist[i]) atomicAdd(st + 16 + i, s_hist[i]);
 }
@@ -103,7 +124,7 @@ __device__ void resolve_classes(const int* cnt, int* map, int* cls) {
 }
 
 struct Resolved {
-    int up_src, lo_src;                     // whose parsing and image the upper / lower routing inputs are cut from: 0 person, 1 clothes
+    int up_src, lo_src;                     // whose parsing and image the upper / lower routing inputs are cut from: 0 person, 1 clothes, 2 lower clothes
     int up_bits, lo_bits, canvas_bits;      // bit g: label group g belongs to the mask (canvas: of the person's parsing)
     int label, bound_start;                 // bound = 255 from row bound_start on (H: nowhere)
 };
@@ -115,7 +136,7 @@ __device__ __forceinline__ int groups_in(const int* map, int a, int b) {
     return m;
 }
 
-// `_host_upper` / `_host_lower` / `_host_full`: every ``if`` on a pixel sum, from the statistics.
+// `_host_upper` / `_host_lower` / `_host_full` / `_host_outfit`: every ``if`` on a pixel sum, from the statistics.
 __device__ void resolve(const int* st, const int* hip, int mode, int H, Resolved& r) {
     int pm[4], pc[4], cm[4], cc[4];
     resolve_classes(st, pm, pc);
@@ -143,6 +164,13 @@ __device__ void resolve(const int* st, const int* hip, int mode, int H, Resolved
         r.canvas_bits = r.up_bits;
         r.label = (!zero && cc[PANTS] > 0) ? 0 : (!zero && cc[SKIRT] > 0) ? 1 : pc[DRESSES] > 0 ? 2 : 1;
         if (ymin >= 0 && !zero) r.bound_start = ymin;
+    } else if (mode == PG_TRYON_OUTFIT) {                                   // `_host_full` with the lower garment's classes from the lower clothes
+        int lm[4], lc[4];
+        resolve_classes(st + kLowerCnt, lm, lc);
+        r.up_src = 1; r.up_bits = groups_in(cm, TOPS, DRESSES);
+        r.lo_src = 2; r.lo_bits = groups_in(lm, PANTS, SKIRT);
+        r.canvas_bits = 0;
+        r.label = lc[PANTS] > 0 ? 0 : lc[SKIRT] > 0 ? 1 : cc[DRESSES] > 0 ? 2 : 1;
     } else {
         r.up_src = r.lo_src = 1;
         r.up_bits = groups_in(cm, TOPS, DRESSES); r.lo_bits = groups_in(cm, PANTS, SKIRT);
@@ -157,7 +185,7 @@ __global__ __launch_bounds__(256) void front_bit_rows_kernel(pg_front_io io, int
     const int n = blockIdx.z, plane = blockIdx.y;
     __shared__ uint32_t s_raw[256];
     __shared__ Resolved s_r;
-    if (plane < 4 ? io.band_absent[n * 4 + plane] != 0 : mode == PG_TRYON_FULL) return;      // (uniform over the workgroup) never read by compose
+    if (plane < 4 ? io.band_absent[n * 4 + plane] != 0 : no_canvas(mode)) return;      // (uniform over the workgroup) never read by compose
     const int rows_pb = 256 / words;
     const int lr = threadIdx.x / words, w = threadIdx.x - lr * words;
     const int y = blockIdx.x * rows_pb + lr;
@@ -364,6 +392,12 @@ __global__ __launch_bounds__(256) void front_compose_kernel(pg_front_io io, int 
     load_src4<1>(io.clothes_parsing + src_row, xs, W, 0u, fast, cp);
     store3(io.image + px * 3, pi[0], pi[1], pi[2]);
     store3(io.clothes + px * 3, ci[0], ci[1], ci[2]);
+    uint32_t li[3] = {0u, 0u, 0u}, lp[1] = {0u};                            // the lower clothes (outfit mode; uniform over the grid)
+    if (mode == PG_TRYON_OUTFIT) {
+        load_src4<3>(io.lower_src_img + src_row * 3, xs, W, 255u, fast, li);
+        load_src4<1>(io.lower_src_parsing + src_row, xs, W, 0u, fast, lp);
+        store3(io.lower_clothes + px * 3, li[0], li[1], li[2]);
+    }
 
     // the routing inputs: garment masks from the resolved classes, the images under them
     bool up_on[4], lo_on[4], can_on[4];
@@ -371,7 +405,7 @@ __global__ __launch_bounds__(256) void front_compose_kernel(pg_front_io io, int 
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int gp = group_of(byte_of(pp, k)), gc = group_of(byte_of(cp, k));
-        const int gu = r.up_src ? gc : gp, gl = r.lo_src ? gc : gp;
+        const int gu = r.up_src ? gc : gp, gl = r.lo_src == 2 ? group_of(byte_of(lp, k)) : r.lo_src ? gc : gp;
         up_on[k] = gu >= 0 && ((r.up_bits >> gu) & 1);
         lo_on[k] = gl >= 0 && ((r.lo_bits >> gl) & 1);
         can_on[k] = gp >= 0 && ((r.canvas_bits >> gp) & 1);
@@ -385,7 +419,8 @@ __global__ __launch_bounds__(256) void front_compose_kernel(pg_front_io io, int 
     store3(io.upper_img + px * 3, (r.up_src ? ci[0] : pi[0]) & m[0], (r.up_src ? ci[1] : pi[1]) & m[1], (r.up_src ? ci[2] : pi[2]) & m[2]);
     rgb_mask(lo_on, m);
     store3(io.lower_mask + px * 3, m[0], m[1], m[2]);
-    store3(io.lower_img + px * 3, (r.lo_src ? ci[0] : pi[0]) & m[0], (r.lo_src ? ci[1] : pi[1]) & m[1], (r.lo_src ? ci[2] : pi[2]) & m[2]);
+    if (r.lo_src == 2) store3(io.lower_img + px * 3, li[0] & m[0], li[1] & m[1], li[2] & m[2]);
+    else store3(io.lower_img + px * 3, (r.lo_src ? ci[0] : pi[0]) & m[0], (r.lo_src ? ci[1] : pi[1]) & m[1], (r.lo_src ? ci[2] : pi[2]) & m[2]);
 
     // canvas: the person's own garment under its mask eroded 8 x 8 -- the pass along y over the x-eroded bit rows (taps -4 .. +3, in the frame)
     const int word = x >> 5, sh = x & 31;                                   // x % 4 == 0: the 4 bits lie in one word
@@ -475,7 +510,8 @@ int check_common(const pg_front_io* io, int n, int H, int W) {
     if (!io->person_img || !io->clothes_img || !io->person_parsing || !io->clothes_parsing || !io->stats) return PG_ERR_INVALID_ARG;
     if (W > H) return PG_ERR_INVALID_ARG;
     if (H % 4 || H > 4096) return PG_ERR_UNSUPPORTED;
-    const void* al[] = {io->person_img, io->clothes_img, io->person_parsing, io->clothes_parsing, io->garment_parsing, io->stats};
+    const void* al[] = {io->person_img, io->clothes_img, io->person_parsing, io->clothes_parsing, io->garment_parsing, io->stats, io->lower_src_img,
+                        io->lower_src_parsing};
     for (const void* p : al)
         if (reinterpret_cast<uintptr_t>(p) & 3u) return PG_ERR_UNSUPPORTED;
     if (n > 65535) return PG_ERR_TOO_LARGE;
@@ -485,7 +521,8 @@ int check_common(const pg_front_io* io, int n, int H, int W) {
 int check_maps(const pg_front_io* io, int n, int H, int W, int left, int mode) {
     const int rc = check_common(io, n, H, W);
     if (rc != PG_OK) return rc;
-    if (mode != PG_TRYON_UPPER && mode != PG_TRYON_LOWER && mode != PG_TRYON_FULL) return PG_ERR_INVALID_ARG;
+    if (mode != PG_TRYON_UPPER && mode != PG_TRYON_LOWER && mode != PG_TRYON_FULL && mode != PG_TRYON_OUTFIT) return PG_ERR_INVALID_ARG;
+    if (mode == PG_TRYON_OUTFIT && (!io->lower_src_img || !io->lower_src_parsing)) return PG_ERR_INVALID_ARG;
     if (left < 0 || left + W > H) return PG_ERR_INVALID_ARG;
     if (!io->bands || !io->band_absent || !io->hip_top || !io->bit_rows) return PG_ERR_INVALID_ARG;
     if ((reinterpret_cast<uintptr_t>(io->bands) & 7u) || (reinterpret_cast<uintptr_t>(io->band_absent) & 3u) ||
@@ -524,9 +561,10 @@ PG_EXPORT int pg_tryon_front_compose(const pg_front_io* io, int n, int H, int W,
     for (const void* p : out)
         if (!p) return PG_ERR_INVALID_ARG;
     if ((io->sleeve != nullptr) != (io->garment_parsing != nullptr)) return PG_ERR_INVALID_ARG;
-    if ((io->canvas != nullptr) != (mode != PG_TRYON_FULL)) return PG_ERR_INVALID_ARG;
+    if ((io->canvas != nullptr) != !no_canvas(mode)) return PG_ERR_INVALID_ARG;
+    if ((io->lower_clothes != nullptr) != (mode == PG_TRYON_OUTFIT)) return PG_ERR_INVALID_ARG;
     const void* al[] = {io->upper_img, io->lower_img, io->upper_mask, io->lower_mask, io->sleeve, io->image, io->clothes, io->pose, io->retain_mask,
-                        io->canvas, io->skin, io->label, io->pose_prims};
+                        io->canvas, io->skin, io->label, io->pose_prims, io->lower_clothes};
     for (const void* p : al)
         if (reinterpret_cast<uintptr_t>(p) & 3u) return PG_ERR_UNSUPPORTED;
     const int words = (H + 31) / 32, fast = (left % 4 == 0 && W % 4 == 0) ? 1 : 0;

@@ -54,7 +54,7 @@ PLUGIN_SOURCES = {
                       'conv2d16_inst_k1x2.hip', 'conv2d16_inst_k3s2.hip', 'conv2d16_inst_up2f.hip', 'conv1x1_head16.hip', 'spade16.hip', 'conv1x1_fold.hip', 'conv3x3_fold.hip', 'optim.hip'],
 }
 
-ABI_VERSION = 20     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
+ABI_VERSION = 21     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
 
 _cached_plugins = dict()
 

@@ -15,6 +15,10 @@ Directory layout (test.py:109-116): ``image/<name>.jpg`` (RGB JPEG, 320x512), ``
 0-19), ``garment_parsing/<name>.png`` (labels in channel 0), ``keypoints/<name>_keypoints.json`` (OpenPose-18:
 ``people[0].pose_keypoints_2d``, 54 floats) and a pairs file with ``<clothes_name> <person_name>`` per line.
 
+part='outfit' is this package's own fourth mode, not one of the reference's: the top of one clothes image and the trousers or skirt of another on one
+person -- 'full' with the lower garment read from a third image.  Its pairs file has ``<upper_clothes_name> <lower_clothes_name> <person_name>`` per
+line; its items are 'full''s 16-tuple (with the upper clothes as the clothes) followed by the lower clothes image [3,512,512] and its name.
+
 What is restated and what is not: the label algebra (garment-class resolution, retain / skin / bound maps) follows the
 reference statement by statement; the 10-part patch routing runs on this package's kernels (training.patch_routing: HIP on a
 GPU, the same arithmetic in NumPy on the CPU).  The reference rasterises the pose map and the palm masks with OpenCV, scikit-image
@@ -160,7 +164,8 @@ class TryOnTestSet(torch.utils.data.Dataset):
     part='upper' (default): the clothes' top (``UvitonDatasetFull_512_test_upper``); the person keeps the lower garment.
     part='lower': the clothes' trousers or skirt (``UvitonDatasetFull_512_test_lower``); the person keeps the top.
     part='full': the clothes' whole outfit (``UvitonDatasetFull_512_test_full``).
-    use_sleeve_mask reads the garment parsing of the image the upper garment comes from: the clothes' (upper, full) or the person's (lower)."""
+    part='outfit': the top of one clothes image and the lower garment of another (`_host_outfit`; three names per line of the pairs file).
+    use_sleeve_mask reads the garment parsing of the image the upper garment comes from: the clothes' (upper, full, outfit) or the person's (lower)."""
 
     def __init__(self, path, test_txt='test_pairs.txt', use_sleeve_mask=False, device='cpu', part='upper'):
         if PIL is None:
@@ -168,12 +173,16 @@ class TryOnTestSet(torch.utils.data.Dataset):
         if part not in patch_routing.TRYON_MODES:
             raise ValueError(f'part must be one of {sorted(patch_routing.TRYON_MODES)}, not {part!r}')
         self.path, self.use_sleeve_mask, self.device, self.part = path, use_sleeve_mask, device, part
-        self.pairs = []
+        self.pairs = []                                      # (clothes_name, person_name), in the outfit mode (clothes_name, person_name, lower_name)
+        count = 3 if part == 'outfit' else 2
         with open(os.path.join(path, test_txt)) as f:
             for line in f:
                 if line.strip():
-                    clothes_name, person_name = line.split()
-                    self.pairs.append((clothes_name, person_name))
+                    names = line.split()
+                    if len(names) != count:
+                        raise ValueError(f"{test_txt}: part={part!r} takes {count} names per line ("
+                                         f"{'<upper> <lower> <person>' if count == 3 else '<clothes> <person>'}), not {line.strip()!r}")
+                    self.pairs.append((names[0], names[-1]) + tuple(names[1:-1]))
         if not self.pairs:
             raise IOError('no pairs listed in ' + test_txt)
 
@@ -306,6 +315,10 @@ class TryOnTestSet(torch.utils.data.Dataset):
         cparsing, _ = _pad_square(self._labels('parsing', clothes_name), 0)
         return clothes, clothes_pose, ckp, cparsing
 
+    def _lower_clothes(self, lower_name):
+        """The outfit mode's second clothes image, as `_clothes` gives the first."""
+        return self._clothes(lower_name)
+
     def _sleeve(self, name):
         return self._sleeve_map(self._labels('garment_parsing', name)) if self.use_sleeve_mask else None
 
@@ -323,8 +336,7 @@ class TryOnTestSet(torch.utils.data.Dataset):
         return None
 
     def __getitem__(self, idx):
-        clothes_name, person_name = self.pairs[idx]
-        return getattr(self, '_item_' + self.part)(clothes_name, person_name)
+        return getattr(self, '_item_' + self.part)(*self.pairs[idx])
 
     def unrouted(self, idx):
         """Everything ``__getitem__`` computes except the patch routing and what depends on its result, for a batched route on the GPU
@@ -339,17 +351,22 @@ class TryOnTestSet(torch.utils.data.Dataset):
                                                        constant along each row in every mode); the upper and full modes finish it from the
                                                        routed canvases (training.tryon.final_bound)
         canvas                                         uint8 [512, 512, 3] or None: the mode's host-computed garment canvas -- the person's eroded
-                                                       lower garment (upper) or eroded top (lower); None in the full mode
-        person_name, clothes_name"""
+                                                       lower garment (upper) or eroded top (lower); None in the full and outfit modes
+        person_name, clothes_name
+        lower_kp, lower_clothes, lower_name            outfit mode only: the lower clothes' key points, image (padded with 255, HWC) and name;
+                                                       clothes, clothes_kp and clothes_name are the upper clothes'"""
         return self._unrouted(*self.pairs[idx])
 
-    def _unrouted(self, clothes_name, person_name):
-        h = getattr(self, '_host_' + self.part)(clothes_name, person_name)
-        up, lo, um, lm, sleeve, ckp, kp = h['routing']
-        return dict(upper_img=up, lower_img=lo, upper_mask=um, lower_mask=lm, sleeve=sleeve, clothes_kp=ckp, person_kp=kp, image=h['image'],
+    def _unrouted(self, clothes_name, person_name, *lower_name):
+        h = getattr(self, '_host_' + self.part)(clothes_name, person_name, *lower_name)
+        up, lo, um, lm, sleeve, ckp, kp = h['routing'][:7]
+        item = dict(upper_img=up, lower_img=lo, upper_mask=um, lower_mask=lm, sleeve=sleeve, clothes_kp=ckp, person_kp=kp, image=h['image'],
                     clothes=h['clothes'], pose=h['pose'], retain_mask=h['retain_mask'], skin=np.array(h['medians'], dtype=np.float64),
                     label=int(h['label']), bound=np.ascontiguousarray(h['bound'][:, 0, 0]), canvas=h['canvas'], person_name=person_name,
                     clothes_name=clothes_name)
+        if lower_name:
+            item.update(lower_kp=h['routing'][7], lower_clothes=h['lower_clothes'], lower_name=lower_name[0])
+        return item
 
     def raw(self, idx):
         """File decoding and keypoint arithmetic only -- what ``training.tryon_front.front_batch`` turns into the ``unrouted`` maps on the GPU.
@@ -363,8 +380,9 @@ class TryOnTestSet(torch.utils.data.Dataset):
         bands, band_absent                 float64 [4, 4, 2], int32 [4]: the `_limb_band` corners of the four arm bands (`ARMS` order, upper arm then
                                            fore-arm) in the padded frame; absent = 1 where a joint is missing (the band is then "all ones")
         hip_top                            `_hip_top` of the person: an int or None (read by the upper mode only)
-        person_name, clothes_name"""
-        clothes_name, person_name = self.pairs[idx]
+        person_name, clothes_name
+        lower_img, lower_parsing, lower_kp, lower_name     outfit mode only: the lower clothes', as clothes_img, clothes_parsing, clothes_kp, clothes_name"""
+        clothes_name, person_name = self.pairs[idx][:2]
         person_img, clothes_img = self._image(person_name), self._image(clothes_name)
         assert person_img.shape[0] == SIDE and clothes_img.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
         table, kp = self.pose_table(self._keypoints(person_name), person_img.shape[:2])
@@ -381,9 +399,17 @@ class TryOnTestSet(torch.utils.data.Dataset):
         garment = None
         if self.use_sleeve_mask:
             garment = self._labels('garment_parsing', person_name if self.part == 'lower' else clothes_name)[..., 0]
-        return dict(person_img=person_img, clothes_img=clothes_img, person_parsing=self._labels('parsing', person_name)[..., 0],
+        item = dict(person_img=person_img, clothes_img=clothes_img, person_parsing=self._labels('parsing', person_name)[..., 0],
                     clothes_parsing=self._labels('parsing', clothes_name)[..., 0], garment_parsing=garment, person_kp=kp, clothes_kp=ckp,
                     pose_prims=table, bands=bands, band_absent=absent, hip_top=self._hip_top(kp), person_name=person_name, clothes_name=clothes_name)
+        if self.part == 'outfit':
+            lower_name = self.pairs[idx][2]
+            lower_img = self._image(lower_name)
+            assert lower_img.shape[0] == SIDE, 'images are 512 pixels high (320 x 512 in the reference data)'
+            _, lkp = self.pose_table(self._keypoints(lower_name), lower_img.shape[:2])
+            lkp[:, 0] += (SIDE - lower_img.shape[1]) // 2
+            item.update(lower_img=lower_img, lower_parsing=self._labels('parsing', lower_name)[..., 0], lower_kp=lkp, lower_name=lower_name)
+        return item
 
     # ------------------------------------------------------------------ the three modes: host half (before the routing), then the rest
     def _host_upper(self, clothes_name, person_name):
@@ -493,6 +519,46 @@ class TryOnTestSet(torch.utils.data.Dataset):
         return self._pack(h['image'], h['clothes'], h['pose'], h['clothes_pose'], norm_img, norm_img_lower, denorm_upper, denorm_lower, h['retain_mask'],
                           self._skin_map(h['medians']), h['label'], bound, person_name, clothes_name)
 
+    def _host_outfit(self, clothes_name, person_name, lower_name):
+        """`_host_full`'s statements with the lower-garment quantities taken from a second clothes image: the top (tops + dresses, the sleeve mask, the
+        key points that route the upper parts) from `clothes_name`, the trousers or skirt and the key points that route lower parts 0, 6 to 9 from
+        `lower_name`.  Nothing is zeroed for a dress: as 'full' routes a clothes image whose parsing holds a dress and pants, both garments are routed."""
+        image, pose, kp, parsing, retain_mask, medians = self._person(person_name)
+        clothes, clothes_pose, ckp, cparsing = self._clothes(clothes_name)
+        lower_clothes, _, lkp, lparsing = self._lower_clothes(lower_name)
+        ctops, cdresses, _, _ = _garment_classes(cparsing)
+        _, _, cpants, cskirt = _garment_classes(lparsing)
+        upper_mask, lower_mask = ctops + cdresses, cskirt + cpants
+        upper_image, lower_image = upper_mask * clothes, lower_mask * lower_clothes
+        upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
+        sleeve = self._sleeve(clothes_name)
+        routing = (upper_image.astype(np.uint8), lower_image.astype(np.uint8), upper_rgb.astype(np.uint8), lower_rgb.astype(np.uint8), sleeve, ckp, kp, lkp)
+        bound = np.zeros((SIDE, SIDE, 1), dtype=np.uint8)    # start of the lower garment: the routed one's top row (after the routing)
+        if cpants.sum() > 0:
+            label = 0.0
+        elif cskirt.sum() > 0:
+            label = 1.0
+        elif cdresses.sum() > 0:                             # a dress on top and no lower garment: no bound
+            label = 2.0
+        else:
+            label = 1.0
+        return dict(routing=routing, image=image, clothes=clothes, pose=pose, clothes_pose=clothes_pose, retain_mask=retain_mask, medians=medians,
+                    label=label, bound=bound, canvas=None, lower_clothes=lower_clothes)
+
+    def _item_outfit(self, clothes_name, person_name, lower_name):
+        h = self._host_outfit(clothes_name, person_name, lower_name)
+        routed = patch_routing.normalize(*h['routing'][:7], 2, device=self.device, part='outfit', lower_keypoints=h['routing'][7])
+        norm_img, norm_img_lower, denorm_upper, denorm_lower = (t.cpu().numpy() for t in routed)
+        bound = h['bound']
+        lower_bbox = _bbox((denorm_lower.sum(axis=2, keepdims=True) > 0).astype(np.uint8))
+        if lower_bbox is not None:
+            bound[lower_bbox[1]:] += 255
+        if h['label'] == 2.0:
+            bound = bound * 0
+        item = self._pack(h['image'], h['clothes'], h['pose'], h['clothes_pose'], norm_img, norm_img_lower, denorm_upper, denorm_lower, h['retain_mask'],
+                          self._skin_map(h['medians']), h['label'], bound, person_name, clothes_name)
+        return item + (np.ascontiguousarray(np.transpose(h['lower_clothes'], (2, 0, 1))), lower_name)
+
     @staticmethod
     def _pack(image, clothes, pose, clothes_pose, norm_img, norm_img_lower, denorm_upper, denorm_lower, retain_mask, skin_average, label, bound,
               person_name, clothes_name):
@@ -519,6 +585,7 @@ def to_generator_inputs(batch, device):
                 denorm_upper_mask=den_up_mask.to(torch.float32), denorm_lower_mask=den_lo_mask.to(torch.float32))
 
 
+_NAME_KEYS, _LOWER_NAME_KEYS = ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'), ('lower_kp', 'lower_name')     # the lists of a batch
 _UNROUTED_ARRAYS = ('upper_img', 'lower_img', 'upper_mask', 'lower_mask', 'sleeve', 'image', 'clothes', 'pose', 'retain_mask', 'bound', 'canvas')
 
 
@@ -526,9 +593,11 @@ def collate_unrouted(items, pin=False):
     """Stack ``TryOnTestSet.unrouted`` items into a batch: the uint8 arrays as [N, ...] tensors (pinned with pin=True -- only in the process that
     owns the GPU; a DataLoader with workers pins them itself with ``pin_memory=True``), skin as float32 [N, 3] (the cast
     ``skin_average.to(torch.float32)`` of test.py:133, NaN kept), label as int32 [N]; keypoints and names stay lists.  Keys whose value is None
-    (sleeve without the sleeve mask, canvas in the full mode) stay None."""
+    (sleeve without the sleeve mask, canvas in the full and outfit modes) stay None.  Outfit items add lower_clothes (after canvas), lower_kp and
+    lower_name (at the end); batches of the other modes do not have these keys."""
+    outfit = 'lower_clothes' in items[0]
     out = {}
-    for k in _UNROUTED_ARRAYS:
+    for k in _UNROUTED_ARRAYS + (('lower_clothes',) if outfit else ()):
         if items[0][k] is None:
             out[k] = None
             continue
@@ -537,26 +606,29 @@ def collate_unrouted(items, pin=False):
     skin = torch.from_numpy(np.stack([it['skin'] for it in items])).to(torch.float32)
     label = torch.tensor([it['label'] for it in items], dtype=torch.int32)
     out['skin'], out['label'] = (skin.pin_memory(), label.pin_memory()) if pin else (skin, label)
-    for k in ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'):
+    for k in _NAME_KEYS + (_LOWER_NAME_KEYS if outfit else ()):
         out[k] = [it[k] for it in items]
     return out
 
 
 _RAW_ARRAYS = ('person_img', 'clothes_img', 'person_parsing', 'clothes_parsing', 'garment_parsing', 'pose_prims', 'bands', 'band_absent')
+_RAW_LOWER_ARRAYS = ('lower_img', 'lower_parsing')    # outfit batches only
 _HIP_CLAMP = 1 << 20                                  # far beyond the frame on either side: the slice ``bound[top:]`` is the same
 
 
 def collate_raw(items, pin=False):
     """Stack ``TryOnTestSet.raw`` items into a batch: the arrays as [N, ...] tensors (pinned with pin=True, as `collate_unrouted`), garment_parsing None
-    without the sleeve mask, hip_top as int32 [N, 2] = (valid, row); keypoints and names stay lists."""
+    without the sleeve mask, hip_top as int32 [N, 2] = (valid, row); keypoints and names stay lists.  Outfit items add lower_img and lower_parsing
+    (after band_absent), lower_kp and lower_name (at the end)."""
+    outfit = 'lower_img' in items[0]
     out = {}
-    for k in _RAW_ARRAYS:
+    for k in _RAW_ARRAYS + (_RAW_LOWER_ARRAYS if outfit else ()):
         out[k] = None if items[0][k] is None else torch.from_numpy(np.stack([it[k] for it in items]))
     out['hip_top'] = torch.tensor([[0, 0] if it['hip_top'] is None else [1, max(-_HIP_CLAMP, min(_HIP_CLAMP, it['hip_top']))] for it in items],
                                   dtype=torch.int32)
     if pin:
         out = {k: (None if v is None else v.pin_memory()) for k, v in out.items()}
-    for k in ('clothes_kp', 'person_kp', 'person_name', 'clothes_name'):
+    for k in _NAME_KEYS + (_LOWER_NAME_KEYS if outfit else ()):
         out[k] = [it[k] for it in items]
     return out
 
@@ -577,13 +649,19 @@ class _RawPair(TryOnTestSet):
         cparsing, _ = _pad_square(it['clothes_parsing'][..., None], 0)
         return clothes, None, it['clothes_kp'].copy(), cparsing         # (no clothes pose map: `unrouted` does not carry it)
 
+    def _lower_clothes(self, lower_name):
+        it = self.item
+        lower, _ = _pad_square(it['lower_img'], 255)
+        lparsing, _ = _pad_square(it['lower_parsing'][..., None], 0)
+        return lower, None, it['lower_kp'].copy(), lparsing
+
     def _sleeve(self, name):
         return self._sleeve_map(self.item['garment_parsing'][..., None]) if self.use_sleeve_mask else None
 
 
 def unrouted_from_raw(item, part):
     """``TryOnTestSet.unrouted`` of a ``raw`` item, through the same host statements (the CPU route of ``training.tryon_front.front_batch``)."""
-    return _RawPair(item, part)._unrouted(item['clothes_name'], item['person_name'])
+    return _RawPair(item, part)._unrouted(item['clothes_name'], item['person_name'], *((item['lower_name'],) if part == 'outfit' else ()))
 
 
 # ------------------------------------------------------------------------------------------------------------- the training set

@@ -20,12 +20,15 @@ part      upper-garment warp        lower-garment warp        erode   lower part
 upper     clothes crop (:2605)      person crop (:2634)       8 x 8   torso / hips (:2654-2663)    5 (+ denorm_upper_img_wo_sleeve)
 lower     person crop (:3361)       clothes crop (:3388)      5 x 5   torso / hips (:3408-3417)    4
 full      clothes crop (:1843)      clothes crop (:1869)      5 x 5   no                           4
+outfit    clothes crop              lower clothes' crop       5 x 5   no                           4
 train     person crop (:1063)       person crop (:1077)       5 x 5   no                           6 (+ the routed clothes masks)
 ========  ========================  ========================  ======  ===========================  ==========================
 
 (upper: dataset.py:2555-2700 ``UvitonDatasetFull_512_test_upper.normalize``; lower: :3313-3454; full: :1796-1923; train: :1010-1195
 ``UvitonDatasetFull_512.normalize``.)  Every de-normalising warp uses the person crop's inverse; the missing-sleeve mirroring is the same in all
-four.  The training mode routes a person through their own key points (self-reconstruction): there is one crop set, computed once; the sleeve
+four.  'outfit' is not one of the reference's modes: it is 'full' with the lower garment cut from a second clothes image, so the lower-garment warps
+(parts 0, 6 to 9) take their crops from that image's key points (`lower_keypoints`); with the clothes' own key points there it is 'full'.
+The training mode routes a person through their own key points (self-reconstruction): there is one crop set, computed once; the sleeve
 mask is always applied; and the routed clothes masks (mirrored like the images) are results too.  Its random erase of the lower-garment patches is
 not part of the routing: the loader draws a decision record and training.train_fetch applies it.
 """
@@ -47,14 +50,23 @@ _J = {name: i for i, name in enumerate(ORDER)}
 # part -> (upper garment warped with the clothes crop?, lower garment warped with the clothes crop?, erode window, lower parts give way to the upper
 # garment?, denorm_upper_img_wo_sleeve returned?)
 MODES = {'upper': (True, False, 8, True, True), 'lower': (False, True, 5, True, False), 'full': (True, True, 5, False, False),
-         'train': (False, False, 5, False, False)}
-TRYON_MODES = ('upper', 'lower', 'full')     # test.py --testpart; 'train' is the training loader's mode (one crop set, masks returned)
+         'train': (False, False, 5, False, False), 'outfit': (True, True, 5, False, False)}
+TRYON_MODES = ('upper', 'lower', 'full', 'outfit')     # test.py --testpart, and 'outfit' (top and bottom from two clothes images); 'train' is the
+                                                        # training loader's mode (one crop set, masks returned)
+LOWER_IDS = (0, 6, 7, 8, 9)                  # the parts the lower garment is routed through
 
 
 def _mode(part):
     if part not in MODES:
         raise ValueError(f"patch_routing: part must be one of {sorted(MODES)}, not {part!r}")
     return MODES[part]
+
+
+def _lower_kp(part, lower_keypoints):
+    """The key points the lower-garment warps read instead of the clothes': part='outfit' only, None = the clothes' own."""
+    if lower_keypoints is not None and part != 'outfit':
+        raise ValueError(f"patch_routing: lower_keypoints belong to part='outfit', not {part!r}")
+    return lower_keypoints
 
 
 class WarpJob(ctypes.Structure):
@@ -399,17 +411,20 @@ def patch_compose_(canvas, patch, mask, canvas2=None, ksize=8):
 
 
 def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, sleeve_mask, clothes_keypoints, person_keypoints, box_factor, device='cuda',
-              part='upper'):
+              part='upper', lower_keypoints=None):
     """The reference's ``normalize`` of try-on mode `part` (module docstring), as uint8 tensors on `device`:
 
     part='upper' (dataset.py:2555-2700): (img [h,w,30], img_lower [h,w,15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img)
     part='lower' (:3313-3454) and part='full' (:1796-1923): (img [h,w,30], img_lower [h,w,15], denorm_upper_img, denorm_lower_img)
+    part='outfit': as 'full'; `lower_img` / `lower_clothes_mask` come from a second clothes image and `lower_keypoints` are that image's key points
+        (None: the clothes' own, which makes it 'full')
     part='train' (:1010-1195): (img, img_lower, denorm_upper_img, denorm_lower_img, clothes_masks [h,w,30], clothes_masks_lower [h,w,15]);
         `clothes_keypoints` is not read (the person is routed through `person_keypoints`), `sleeve_mask` is required
 
     (h, w = H / 2**box_factor, W / 2**box_factor; the canvases are [H, W, 3].)"""
     up_by_clothes, lo_by_clothes, ksize, lower_minus_upper, wo_sleeve = _mode(part)
     train = part == 'train'
+    lower_keypoints = _lower_kp(part, lower_keypoints)
     if train and sleeve_mask is None:
         raise ValueError("patch_routing: part='train' needs the sleeve mask (dataset.py:1063-1067 applies it unconditionally)")
     dev = torch.device(device)
@@ -433,6 +448,9 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
     # stage 1: image -> patch (the upper / lower garment through the clothes' or the person's crop, as the mode says)
     up_m = [c[0][0] if up_by_clothes else c[1][0] for c in crops]
     lo_m = [c[0][0] if lo_by_clothes else c[1][0] for c in crops]
+    if lower_keypoints is not None:                          # outfit: the lower garment through its own image's crops
+        for ii in LOWER_IDS:
+            lo_m[ii] = get_crop(lower_keypoints, BPARTS[ii], wh, o_w, o_h, 0.5 if ii < 6 else 0.4)[0]
     jobs, slot = [], {}
     for ii in range(10):
         if up_m[ii] is not None:
@@ -447,7 +465,7 @@ def normalize(upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, slee
     get = lambda kind, ii: out1[slot[(kind, ii)]] if (kind, ii) in slot else zeros()
     part_imgs = [get('img', ii) for ii in range(10)]
     part_masks = [get('mask', ii) for ii in range(10)]
-    lower_ids = [0, 6, 7, 8, 9]
+    lower_ids = list(LOWER_IDS)
     part_imgs_lower = [get('img_lower', ii) for ii in lower_ids]
     part_masks_lower = [get('mask_lower', ii) for ii in lower_ids]
 
@@ -511,8 +529,9 @@ def normalize_batch(samples, box_factor, device='cuda', part='upper'):
     homographies of all samples from one batched solve and the bookkeeping around them as a handful of batched tensor operations.
 
     samples: list of (upper_img, lower_img, upper_clothes_mask, lower_clothes_mask, sleeve_mask | None, clothes_keypoints, person_keypoints), images uint8
-    [H, W, 3] (all the same size).  Returns the results of `normalize(..., part=part)`, stacked -- part='upper': img [N, h, w, 30], img_lower
-    [N, h, w, 15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img [N, H, W, 3]; part='lower' / 'full': the same without
+    [H, W, 3] (all the same size); part='outfit' takes an eighth entry, the lower clothes' key points (absent or None: the clothes' own, i.e. 'full').
+    Returns the results of `normalize(..., part=part)`, stacked -- part='upper': img [N, h, w, 30], img_lower
+    [N, h, w, 15], denorm_upper_img, denorm_upper_img_wo_sleeve, denorm_lower_img [N, H, W, 3]; part='lower' / 'full' / 'outfit': the same without
     denorm_upper_img_wo_sleeve; part='train': those four plus clothes_masks [N, h, w, 30] and clothes_masks_lower [N, h, w, 15] -- bit-identical to the
     per-sample calls (tests/test_patch_routing.py, tests/test_routing_modes_gpu.py, tests/test_train_fetch_gpu.py).  Every mode is the same three
     launches; the mode only picks which crop warps which garment, the erode window, the masking of the lower parts and what is returned."""
@@ -520,10 +539,11 @@ def normalize_batch(samples, box_factor, device='cuda', part='upper'):
     train = part == 'train'
     if train and any(s[4] is None for s in samples):
         raise ValueError("patch_routing: part='train' needs the sleeve mask of every sample")
+    lower_kps = [_lower_kp(part, s[7] if len(s) > 7 else None) for s in samples]
     dev = torch.device(device)
     n = len(samples)
     if dev.type != 'cuda':
-        outs = [normalize(*s, box_factor, device=device, part=part) for s in samples]
+        outs = [normalize(*s[:7], box_factor, device=device, part=part, lower_keypoints=lk) for s, lk in zip(samples, lower_kps)]
         return tuple(torch.stack([o[i] for o in outs]) for i in range(len(outs[0])))
     lib = _init().lib
     ups = torch.stack([_gpu_u8(s[0], dev) for s in samples])
@@ -547,26 +567,33 @@ def normalize_batch(samples, box_factor, device='cuda', part='upper'):
 
     # ---- host geometry: the quadrilaterals per sample and part, then every homography in one batched solve
     part_dst = np.float32(wh * np.float32([[0.0, 0.0], [0.0, 1.0], [1.0, 1.0], [1.0, 0.0]]))
-    cq, pq = {}, {}
+    cq, pq, lq = {}, {}, {}                                  # quadrilaterals of the clothes', the person's and (outfit) the lower clothes' key points
     for i, s in enumerate(samples):
         for ii, bpart in enumerate(BPARTS):
             ar = 0.5 if ii < 6 else 0.4
-            for store, kp in ((pq, s[6]),) if train else ((cq, s[5]), (pq, s[6])):      # (train: clothes and person are one crop set, computed once)
+            stores = ((pq, s[6]),) if train else ((cq, s[5]), (pq, s[6]))               # (train: clothes and person are one crop set, computed once)
+            if lower_kps[i] is not None and ii in LOWER_IDS:
+                stores += ((lq, lower_kps[i]),)
+            for store, kp in stores:
                 q = get_crop(kp, bpart, wh, o_w, o_h, ar, _quad_only=True)
                 if not isinstance(q, tuple):
                     store[(i, ii)] = q
-    ckeys, pkeys = list(cq), list(pq)
-    src = [cq[k] for k in ckeys] + [pq[k] for k in pkeys] + [part_dst] * len(pkeys)
-    dst = [part_dst] * (len(ckeys) + len(pkeys)) + [pq[k] for k in pkeys]
+    ckeys, pkeys, lkeys = list(cq), list(pq), list(lq)
+    src = [cq[k] for k in ckeys] + [pq[k] for k in pkeys] + [part_dst] * len(pkeys) + [lq[k] for k in lkeys]
+    dst = [part_dst] * (len(ckeys) + len(pkeys)) + [pq[k] for k in pkeys] + [part_dst] * len(lkeys)
     mats = perspective_transforms(np.stack(src), np.stack(dst)) if src else np.zeros((0, 3, 3))
     invs = invert3x3_batch(mats).reshape(-1, 9)              # what the warp kernel takes: the inverse of the matrix cv2.warpPerspective is given
     c_m = {k: invs[j] for j, k in enumerate(ckeys)}
     p_m = {k: invs[len(ckeys) + j] for j, k in enumerate(pkeys)}
     p_inv = {k: invs[len(ckeys) + len(pkeys) + j] for j, k in enumerate(pkeys)}
     up_m, lo_m = (c_m if up_by_clothes else p_m), (c_m if lo_by_clothes else p_m)
+    own = {i for i, lk in enumerate(lower_kps) if lk is not None}
+    if own:                         # outfit: those samples' lower warps go through the lower clothes' crops (a part missing there stays missing)
+        lo_m = {k: v for k, v in lo_m.items() if k[0] not in own}
+        lo_m.update({k: invs[len(ckeys) + 2 * len(pkeys) + j] for j, k in enumerate(lkeys)})
 
     # ---- stage 1: image -> patch.  Slots of P1: part images 0..9, part masks 10..19, lower images 20..24, lower masks 25..29 (missing parts stay zero)
-    lower_ids = [0, 6, 7, 8, 9]
+    lower_ids = list(LOWER_IDS)
     P1 = torch.zeros([n, 30, h, w, 3], dtype=torch.uint8, device=dev)
     P2 = torch.empty([n, 30, o_h, o_w, 3], dtype=torch.uint8, device=dev)
     p1, p2 = P1.data_ptr(), P2.data_ptr()

@@ -13,6 +13,10 @@ Per batch, on a GPU:
    pinned host memory -- the batch's only host sync is waiting for that copy;
 6. a thread pool encodes the PNGs (Pillow, RGB, compress_level=1) while the next batch runs.
 
+The outfit mode (``--testpart outfit``; this package's own: the top of one clothes image, the trousers or skirt of another, pairs-file lines of
+``<upper> <lower> <person>``) goes the same way; the routing takes the lower clothes' key points for the lower parts, the bound rule is the full mode's,
+and step 5 packs four panels, upper clothes | lower clothes | person | result (``pg_tryon_panels_u8``), into ``person___upper___lower.png``.
+
 ``device='cpu'`` runs the same flow through plain torch and NumPy: ``normalize_batch``'s CPU route, the inputs as ``to_generator_inputs`` computes them,
 and ``triptych_numpy``.
 
@@ -35,11 +39,11 @@ from . import dataset as ds_mod
 from . import networks
 from . import patch_routing
 
-MODE_CODE = {'upper': 0, 'lower': 1, 'full': 2}       # enum pg_tryon_mode
+MODE_CODE = {'upper': 0, 'lower': 1, 'full': 2, 'outfit': 3}      # enum pg_tryon_mode
 X0, CW = 96, 320                                      # the columns test.py keeps of each image (test.py:179-180)
 _INV = np.float32(1.0) / np.float32(127.5)            # torch's GPU `t / 127.5` multiplies by this
 
-launch_counter = None     # a dict(row_extent=0, inputs=0, triptych=0) counts the native launches of this module (tests, tools/tryon_bench.py)
+launch_counter = None     # a dict(row_extent=0, inputs=0, triptych=0, panels=0) counts the native launches of this module (tests, tools/tryon_bench.py)
 
 
 class TryonIO(ctypes.Structure):
@@ -63,13 +67,15 @@ def _init():
         lib.pg_tryon_inputs.argtypes = [ctypes.POINTER(TryonIO)] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
         lib.pg_tryon_triptych_u8.restype = ctypes.c_int
         lib.pg_tryon_triptych_u8.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+        lib.pg_tryon_panels_u8.restype = ctypes.c_int
+        lib.pg_tryon_panels_u8.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
         _plugin = plugin
     return _plugin
 
 
 def _count(name):
     if launch_counter is not None:
-        launch_counter[name] += 1
+        launch_counter[name] = launch_counter.get(name, 0) + 1
 
 
 def _check_u8(name, t, dev, ndim):
@@ -144,29 +150,57 @@ def triptych(finetune_img, clothes, image):
     return out
 
 
+def panels(finetune_img, sources):
+    """source 0 | ... | source k-1 | result, columns 96:416 of each, uint8 RGB [N, H, (k + 1) * 320, 3]; every panel with `triptych`'s arithmetic.  The
+    outfit mode's sources are (upper clothes, lower clothes, person).  GPU: one launch of pg_tryon_panels_u8; CPU: ``panels_numpy``."""
+    sources = list(sources)
+    if finetune_img.device.type != 'cuda':
+        return torch.from_numpy(panels_numpy(finetune_img.detach().numpy(), [s.numpy() for s in sources]))
+    dev = finetune_img.device
+    fin = finetune_img.detach().to(torch.float32).contiguous()
+    n, _, H, W = fin.shape
+    for i, s in enumerate(sources):
+        _check_u8(f'sources[{i}]', s, dev, 4)
+        if tuple(s.shape) != (n, H, W, 3):
+            raise nat.NativeOpError(f'tryon: sources[{i}] must have shape {(n, H, W, 3)}, not {tuple(s.shape)}')
+    k = len(sources)
+    out = torch.empty([n, H, (k + 1) * CW, 3], dtype=torch.uint8, device=dev)
+    ptrs = (ctypes.c_void_p * k)(*[s.data_ptr() for s in sources])
+    with torch.cuda.device(dev):
+        nat.check(_init().lib.pg_tryon_panels_u8(fin.data_ptr(), ptrs, k, out.data_ptr(), n, H, W, X0, CW, nat.stream_of(fin)), 'pg_tryon_panels_u8')
+    _count('panels')
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------- the CPU route
 
 def triptych_numpy(finetune_img, clothes, image):
     """test.py:162-181 in NumPy for a batch: finetune_img float32 [N, 3, H, W], clothes / image uint8 [N, H, W, 3] -> uint8 [N, H, 960, 3]."""
+    return panels_numpy(finetune_img, [clothes, image])
+
+
+def panels_numpy(finetune_img, sources):
+    """`triptych_numpy`'s statements for any number of source images: finetune_img float32 [N, 3, H, W], sources uint8 [N, H, W, 3] each ->
+    uint8 [N, H, (k + 1) * 320, 3]."""
     gen = (finetune_img.transpose(0, 2, 3, 1) + 1.0) * 127.5
     gen = np.clip(gen, 0, 255)
     gen = np.where(np.isnan(gen), np.float32(0), gen).astype(np.uint8)                    # NaN -> 0 (documented rule)
     src = lambda u: (((u.astype(np.float32) * _INV - np.float32(1)) + 1.0) * 127.5).astype(np.uint8)
     sl = slice(X0, X0 + CW)
-    return np.ascontiguousarray(np.concatenate([src(clothes)[:, :, sl], src(image)[:, :, sl], gen[:, :, sl]], axis=2))
+    return np.ascontiguousarray(np.concatenate([src(s)[:, :, sl] for s in sources] + [gen[:, :, sl]], axis=2))
 
 
 def final_bound(bound_rows, extents, label, part):
     """The post-routing bound rules on the host rows [N, H] uint8 (what pg_tryon_inputs applies): upper -- ``bound[0:ymax] *= 0`` with ymax the last
-    row of denorm_upper_img_wo_sleeve (dataset.py:2688-2690); full -- ``bound[ymin:] += 255`` from the routed lower garment, and ``bound * 0`` for a
-    dress (label 2, dataset.py:1895-1907); lower -- unchanged.  An extent of -1 (empty canvas) changes nothing."""
+    row of denorm_upper_img_wo_sleeve (dataset.py:2688-2690); full and outfit -- ``bound[ymin:] += 255`` from the routed lower garment, and
+    ``bound * 0`` for a dress (label 2, dataset.py:1895-1907); lower -- unchanged.  An extent of -1 (empty canvas) changes nothing."""
     b = bound_rows.to(torch.int32)
     rows = torch.arange(b.shape[1], dtype=torch.int32, device=b.device)[None]
     ext = extents.to(torch.int32).to(b.device)
     if part == 'upper':
         ymax = ext[:, 1:2]
         b = torch.where((ymax >= 0) & (rows < ymax), 0, b)
-    elif part == 'full':
+    elif part in ('full', 'outfit'):
         ymin = ext[:, 0:1]
         b = torch.where((ymin >= 0) & (rows >= ymin), (b + 255) % 256, b)
         b = torch.where(label.to(b.device)[:, None] == 2, 0, b)
@@ -200,9 +234,11 @@ def loader_tuple(batch, routed, extents, part):
 # ------------------------------------------------------------------------------------------------------------- one batch
 
 def _routing_samples(batch):
+    """The samples of ``normalize_batch``; an outfit batch's carry the lower clothes' key points as an eighth entry."""
     sl = batch['sleeve']
+    lower = [(kp,) for kp in batch['lower_kp']] if 'lower_kp' in batch else [()] * len(batch['person_name'])
     return [(batch['upper_img'][i], batch['lower_img'][i], batch['upper_mask'][i], batch['lower_mask'][i], None if sl is None else sl[i],
-             batch['clothes_kp'][i], batch['person_kp'][i]) for i in range(len(batch['person_name']))]
+             batch['clothes_kp'][i], batch['person_kp'][i]) + lower[i] for i in range(len(batch['person_name']))]
 
 
 def upload(batch, device):
@@ -227,13 +263,21 @@ def batch_inputs(batch, routed, extents, part):
     return generator_inputs(batch, routed[0], routed[1], den_up, den_lo, extents, part)
 
 
+def pack(finetune_img, batch, part):
+    """The result image of a batch: the triptych, or in the outfit mode the four panels upper clothes | lower clothes | person | result."""
+    if part == 'outfit':
+        return panels(finetune_img, (batch['clothes'], batch['lower_clothes'], batch['image']))
+    return triptych(finetune_img, batch['clothes'], batch['image'])
+
+
 def tryon_batch(batch, G, part):
-    """One uploaded batch -> triptych uint8 [N, 512, 960, 3] on the batch's device (routing, inputs, generator, packing)."""
+    """One uploaded batch -> triptych uint8 [N, 512, 960, 3] (outfit: the four panels, [N, 512, 1280, 3]) on the batch's device (routing, inputs,
+    generator, packing)."""
     routed, ext = route(batch, part)
     inp = batch_inputs(batch, routed, ext, part)
     with torch.no_grad():
         _, finetune_img, _ = G(**inp, noise_mode='const')
-    return triptych(finetune_img, batch['clothes'], batch['image'])
+    return pack(finetune_img, batch, part)
 
 
 # ------------------------------------------------------------------------------------------------------------- driver
@@ -274,9 +318,10 @@ FRONTS = ('host', 'native')
 PRECISIONS = {'fp32': None, 'bf16': torch.bfloat16, 'fp16': torch.float16}
 
 
-def result_name(person_name, clothes_name):
-    """test.py:183-186: the base names without their 4-character extensions."""
-    return person_name.split('/')[-1][:-4] + '___' + clothes_name.split('/')[-1][:-4] + '.png'
+def result_name(person_name, clothes_name, lower_name=None):
+    """test.py:183-186: the base names without their 4-character extensions; the outfit mode appends the lower clothes' (person___upper___lower.png)."""
+    base = lambda name: name.split('/')[-1][:-4]
+    return '___'.join([base(person_name), base(clothes_name)] + ([] if lower_name is None else [base(lower_name)])) + '.png'
 
 
 def _write_png(path, rgb):
@@ -322,8 +367,8 @@ def _run_tryon(dataset, G, outdir, batch_size, device, workers, stats, front):
         if done is not None:
             done.synchronize()
         arr = host.numpy()
-        for i, (pn, cn) in enumerate(names):
-            path = os.path.join(outdir, result_name(pn, cn))
+        for i, pair in enumerate(names):
+            path = os.path.join(outdir, result_name(*pair))
             pending.append(pool.submit(_write_png, path, arr[i]))
             written.append(path)
 
@@ -338,7 +383,7 @@ def _run_tryon(dataset, G, outdir, batch_size, device, workers, stats, front):
                 stats.setdefault('load_s', []).append(time.perf_counter() - t0)
             if host_batch is None:
                 break
-            names = list(zip(host_batch['person_name'], host_batch['clothes_name']))
+            names = list(zip(host_batch['person_name'], host_batch['clothes_name'], *([host_batch['lower_name']] if 'lower_name' in host_batch else [])))
             if cuda:
                 with torch.cuda.device(dev):
                     ev = []
@@ -359,7 +404,7 @@ def _run_tryon(dataset, G, outdir, batch_size, device, workers, stats, front):
                     with torch.no_grad():
                         _, finetune_img, _ = G(**inp, noise_mode='const')
                     mark()
-                    trip = triptych(finetune_img, batch['clothes'], batch['image'])
+                    trip = pack(finetune_img, batch, dataset.part)
                     mark()
                     if stats is not None:
                         stats.setdefault('events', []).append(ev)
@@ -386,8 +431,10 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description='Try garments on people with a PASTA-GAN++ snapshot (the reference\'s test.py).')
     p.add_argument('--network', required=True, help='network-snapshot-*.pkl (read without executing anything in it)')
     p.add_argument('--dataroot', required=True, help='test data directory (image/, parsing/, garment_parsing/, keypoints/, the pairs file)')
-    p.add_argument('--testtxt', default='test_pairs.txt', help='pairs file in --dataroot: "<clothes> <person>" per line')
-    p.add_argument('--testpart', required=True, choices=sorted(MODE_CODE), help='what is transferred: upper garment, lower garment or the full outfit')
+    p.add_argument('--testtxt', default='test_pairs.txt', help='pairs file in --dataroot: "<clothes> <person>" per line ("<upper> <lower> <person>" with '
+                   '--testpart outfit)')
+    p.add_argument('--testpart', required=True, choices=sorted(MODE_CODE), help='what is transferred: upper garment, lower garment, the full outfit of one '
+                   'clothes image, or (outfit) the top of one clothes image and the lower garment of another')
     p.add_argument('--batchsize', type=int, default=1)
     p.add_argument('--use-sleeve-mask', action='store_true')
     p.add_argument('--outdir', required=True, help='where the PNGs go')

@@ -3,7 +3,8 @@
     python tryon.py --dataroot test_datas --testtxt test_pairs.txt --network network-snapshot-004408.pkl \
         --outdir test_results/upper --batchsize 1 --testpart upper --use-sleeve-mask [--device cuda] [--workers 4]
 
-Writes one PNG per pair: clothes | person | result (training/tryon.py)."""
+Writes one PNG per pair: clothes | person | result (training/tryon.py).  ``--testpart outfit`` (not one of the reference's) takes the top of one clothes
+image and the trousers or skirt of another: pairs-file lines of ``<upper> <lower> <person>``, PNGs of upper clothes | lower clothes | person | result."""
 
 import os
 import sys

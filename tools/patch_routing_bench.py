@@ -1,5 +1,6 @@
 """Dev tool (GPU box): throughput of training.patch_routing on synthetic 512x512 samples, inputs resident on the GPU -- `normalize_batch` (a batch
-of 16, the route config3_routed takes) and the per-sample `normalize`, for the try-on mode given by --part (upper | lower | full | all).
+of 16, the route config3_routed takes) and the per-sample `normalize`, for the mode given by --part (upper | lower | full | outfit | train | all; outfit
+routes the lower garment through a second set of key points).
 Reports per batch the device time of the routing with the host work hidden (bench.py's config3_routed figure), the host wall time, the native
 launches and the algorithmic bytes."""
 import argparse, json, os, sys, time
@@ -22,12 +23,16 @@ up, lo = (torch.from_numpy(rng.integers(0, 256, (512, 512, 3), dtype=np.uint8)).
 um = torch.zeros(512, 512, 3, dtype=torch.uint8, device='cuda'); um[90:310, 150:370] = 255
 lm = torch.zeros(512, 512, 3, dtype=torch.uint8, device='cuda'); lm[270:505, 190:330] = 255
 samples = [(up * (um > 0), lo * (lm > 0), um, lm, None, keypoints(rng, 8.0), keypoints(rng, 8.0)) for _ in range(args.batch)]
+samples8 = [s + (keypoints(rng, 8.0),) for s in samples]            # outfit: the lower clothes' key points as the eighth entry
 
 c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 c0.record(); torch.cuda._sleep(10 ** 7); c1.record(); torch.cuda.synchronize()
 spin_per_ms = 1e7 / max(c0.elapsed_time(c1), 1e-3)                 # the spin kernel's clock (shader or constant-rate counter)
 
 for part in (sorted(P.MODES) if args.part == 'all' else [args.part]):
+    samples = samples8 if part == 'outfit' else [s[:7] for s in samples8]
+    if part == 'train':                                            # the training mode applies a sleeve mask unconditionally: an empty one
+        samples = [s[:4] + (torch.zeros(512, 512, 1, dtype=torch.uint8, device='cuda'),) + s[5:] for s in samples]
     for _ in range(3):
         P.normalize_batch(samples, 2, part=part)
     torch.cuda.synchronize()
@@ -54,7 +59,7 @@ for part in (sorted(P.MODES) if args.part == 'all' else [args.part]):
     P.traffic_counter = None
     t0 = time.perf_counter()
     for s in samples:
-        P.normalize(*s, 2, part=part)
+        P.normalize(*s[:7], 2, part=part, lower_keypoints=s[7] if len(s) > 7 else None)
     torch.cuda.synchronize()
     sample_ms = (time.perf_counter() - t0) / len(samples) * 1e3
     print(json.dumps(dict(part=part, batch=args.batch, gpu_ms_per_batch=round(batch_ms, 3), host_wall_ms_per_batch=round(wall_ms, 2), launches_per_batch=launches, algorithmic_mb_per_batch=round(nbytes / 1e6, 1),

@@ -4,7 +4,8 @@ Writes K synthetic pairs in the reference's file formats to a temporary director
 (deterministic weights, or --network), and reports as one JSON line:
   - end-to-end images/s of ``run_tryon`` (after one warm-up pass), with the worker count;
   - host ms per sample of the loader's unrouted half (``TryOnTestSet.unrouted``, one process);
-  - GPU ms per batch from events around routing, inputs (row extents + pg_tryon_inputs), generator and triptych;
+  - GPU ms per batch from events around routing, inputs (row extents + pg_tryon_inputs), generator and triptych (--part outfit: the four panels,
+    pg_tryon_panels_u8, under the same keys);
   - launches per batch of the three tryon kernels, the device time and achieved GB/s of pg_tryon_inputs and pg_tryon_triptych_u8 alone;
   - an A/B on the same batch against the existing path: the loader's 16-tuple (pinned, float64 skin / label maps) through ``to_generator_inputs`` and
     test.py's host triptych (finetune_img, image and clothes to the host as float32, NumPy), against pg_tryon_inputs + pg_tryon_triptych_u8 + one copy
@@ -33,8 +34,9 @@ JOINTS = dict(cnose=(160, 60), cneck=(160, 110), rshoulder=(104, 120), relbow=(8
               reye=(150, 50), leye=(170, 50), rear=(140, 55), lear=(180, 55))
 
 
-def write_pairs(root, k, seed=0):
-    """k synthetic people (noise photo, blocky LIP parsing, garment parsing, jittered OpenPose-18), paired i -> i+1."""
+def write_pairs(root, k, seed=0, outfit=False):
+    """k synthetic people (noise photo, blocky LIP parsing, garment parsing, jittered OpenPose-18), paired i -> i+1; outfit: lines of three names, the
+    upper clothes i+1 and the lower clothes i+2 on person i."""
     import PIL.Image
     rng = np.random.default_rng(seed)
     for d in ('image', 'parsing', 'garment_parsing', 'keypoints'):
@@ -62,7 +64,7 @@ def write_pairs(root, k, seed=0):
         names.append(name + '.jpg')
     with open(os.path.join(root, 'test_pairs.txt'), 'w') as f:
         for i in range(k):
-            f.write(f'{names[(i + 1) % k]} {names[i]}\n')
+            f.write(f'{names[(i + 1) % k]} {names[(i + 2) % k]} {names[i]}\n' if outfit else f'{names[(i + 1) % k]} {names[i]}\n')
 
 
 def _device_ms(fn, reps):
@@ -81,7 +83,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--pairs', type=int, default=64)
-    ap.add_argument('--part', default='upper', choices=['upper', 'lower', 'full'])
+    ap.add_argument('--part', default='upper', choices=['upper', 'lower', 'full', 'outfit'])
     ap.add_argument('--workers', type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument('--dataroot')
     ap.add_argument('--network')
@@ -100,7 +102,7 @@ def main():
     if root is None:
         tmp = tempfile.TemporaryDirectory()
         root = tmp.name
-        write_pairs(root, args.pairs)
+        write_pairs(root, args.pairs, outfit=args.part == 'outfit')
     ds = TryOnTestSet(root, use_sleeve_mask=True, part=args.part)
     if args.network:
         G = tryon.build_generator(args.network, dev)
@@ -121,7 +123,7 @@ def main():
         tryon.run_tryon(ds, G, od, batch_size=args.batch, device=dev, workers=args.workers)
         torch.cuda.synchronize()
         stats = {}
-        tryon.launch_counter = dict(row_extent=0, inputs=0, triptych=0)
+        tryon.launch_counter = dict(row_extent=0, inputs=0, triptych=0, panels=0)
         t0 = time.perf_counter()
         files = tryon.run_tryon(ds, G, od, batch_size=args.batch, device=dev, workers=args.workers, stats=stats)
         torch.cuda.synchronize()
@@ -149,8 +151,9 @@ def main():
     out['inputs_kernel'] = dict(ms=round(inp_ms, 4), MB=round(moved / 1e6, 1), GBps=round(moved / inp_ms / 1e6, 1))
     with torch.no_grad():
         _, fin, _ = G(**inp, noise_mode='const')
-    tri_ms = _device_ms(lambda: tryon.triptych(fin, batch['clothes'], batch['image']), 50)
-    tmoved = fin.numel() * 4 // 512 * 320 + 2 * n * 512 * 320 * 3 + n * 512 * 960 * 3
+    k = 3 if args.part == 'outfit' else 2                                                               # source panels
+    tri_ms = _device_ms(lambda: tryon.pack(fin, batch, args.part), 50)
+    tmoved = fin.numel() * 4 // 512 * 320 + k * n * 512 * 320 * 3 + n * 512 * (k + 1) * 320 * 3
     out['triptych_kernel'] = dict(ms=round(tri_ms, 4), MB=round(tmoved / 1e6, 1), GBps=round(tmoved / tri_ms / 1e6, 1))
 
     tup = [t.cpu().contiguous().pin_memory() for t in tryon.loader_tuple(batch, routed, ext, args.part)]        # what test.py's DataLoader hands over
@@ -165,11 +168,11 @@ def main():
             b = ((cl[ii].transpose(1, 2, 0) + 1.0) * 127.5).astype(np.uint8)
             np.concatenate([b[:, 96:416], a[:, 96:416], g[:, 96:416]], axis=1)
 
-    host = torch.empty([n, 512, 960, 3], dtype=torch.uint8, pin_memory=True)
+    host = torch.empty([n, 512, (k + 1) * 320, 3], dtype=torch.uint8, pin_memory=True)
 
     def new():
         tryon.generator_inputs(batch, routed[0], routed[1], den_up, den_lo, ext, args.part)
-        host.copy_(tryon.triptych(fin, batch['clothes'], batch['image']), non_blocking=True)
+        host.copy_(tryon.pack(fin, batch, args.part), non_blocking=True)
         torch.cuda.synchronize()
 
     def wall_ms(fn, reps=5):

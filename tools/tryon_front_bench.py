@@ -34,7 +34,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--pairs', type=int, default=64)
-    ap.add_argument('--part', default='upper', choices=['upper', 'lower', 'full'])
+    ap.add_argument('--part', default='upper', choices=['upper', 'lower', 'full', 'outfit'])
     ap.add_argument('--workers', type=int, default=8)
     ap.add_argument('--rounds', type=int, default=2, help='timed end-to-end passes per front (alternating)')
     ap.add_argument('--small', action='store_true', help='a narrow generator (a rehearsal of the tool, not a measurement)')
@@ -54,7 +54,7 @@ def main():
     if root is None:
         tmp = tempfile.TemporaryDirectory()
         root = tmp.name
-        write_pairs(root, args.pairs)
+        write_pairs(root, args.pairs, outfit=args.part == 'outfit')
     ds = TryOnTestSet(root, use_sleeve_mask=True, part=args.part)
     base, w_dim = (4096, 64) if args.small else (32768, 512)
     G = fill_module_(PN.GeneratorFull_v20(z_dim=0, c_dim=512, w_dim=w_dim, img_resolution=512, img_channels=3, mapping_kwargs=dict(num_layers=1),
