@@ -17,6 +17,7 @@
  *   tryon_front_plugin.so   pg_tryon_front_stats, pg_tryon_front_bit_rows, pg_tryon_front_compose
  *   vgg_loss_plugin.so      pg_maxpool2x2, pg_maxpool2x2_backward, pg_l1_pair_blocks, pg_l1_pair_sum, pg_l1_pair_grad
  *   image_metrics_plugin.so pg_image_pair_metrics_workspace, pg_image_pair_metrics_u8
+ *   region_metrics_plugin.so pg_region_pair_metrics_workspace, pg_region_pair_metrics_u8, pg_label_confusion_u8
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 21
+#define PG_ABI_VERSION 22
 
 enum pg_dtype { PG_F32 = 0, PG_F16 = 1, PG_BF16 = 2, PG_F64 = 3 };
 
@@ -869,6 +870,64 @@ int64_t pg_image_pair_metrics_workspace(const pg_metric_pair* jobs_host, int npa
 int pg_image_pair_metrics_u8(const pg_metric_pair* jobs_host, const pg_metric_pair* jobs_device, int npairs, void* workspace,
                              int64_t* sad, int64_t* ssd, float* ssim, void* stream);
 int pg_image_metrics_abi_version(void);
+
+/* region_metrics_plugin.so -- the reconstruction metrics restricted to label regions, and the confusion count of two label maps
+ * (torch_utils/ops/region_metrics.py, training/metrics.py, calc_metrics.py).
+ *
+ * A pg_region_pair is a pg_metric_pair plus `labels`: a uint8 [h, w] window (one label per pixel) with its own row stride and a pixel stride >= 1.
+ * A region is a 32-bit set over the label values 0..31 (bit v set: label v belongs to it); a label >= 32 is in no region; regions may overlap.
+ * Per pair j and region r, in ONE pass over the bytes of a, b and labels (the same 32 x 32-position tiles, per-tile origins and filter as the
+ * image_metrics plugin):
+ *   n          pixels whose label is in the region;
+ *   sad, ssd   sum |a - b| and sum (a - b)^2 over those pixels and all channels, exact;
+ *   positions  valid SSIM positions (y < h - 10, x < w - 10) whose centre pixel (y + 5, x + 5) is in the region;
+ *   ssim_sum   the sum of the SSIM map (image_metrics definitions) over those positions and all channels, float64.
+ * A region holding every label gives the sad / ssd of pg_image_pair_metrics_u8 and ssim_sum / (positions * channels) = its SSIM up to rounding.
+ * No byte outside a window is read, nothing need be aligned; no atomics (bit-identical run to run, and a pair's result does not depend on the
+ * other pairs of the call); every pixel is counted once across tile seams; nothing is read to the host.
+ * The job table is given twice, as for pg_image_pair_metrics_u8; `regions` are `nregions` host words, read by the call itself.
+ * pg_region_pair_metrics_workspace: bytes of `workspace` for that table and region count (need not be initialised), or a negative PG_ERR_*.
+ * pg_region_pair_metrics_u8: counts[q][j][r] (int64, q = 0 n, 1 sad, 2 ssd, 3 positions: [4, npairs, nregions]) and ssim_sum[j][r] (float64).
+ *   Two launches.  PG_ERR_INVALID_ARG for npairs <= 0, nregions outside 1..PG_REGION_MAX, a NULL table or pointer, h or w < 11, channels outside
+ *   {1, 3}, a / b pix_stride < channels, labels pix_stride < 1 or a row_stride < 1; PG_ERR_TOO_LARGE for h * w * channels >= 2^31 or
+ *   npairs > PG_METRIC_MAX_PAIRS.
+ *
+ * pg_label_confusion_u8: a pg_label_pair is two uint8 [h, w] windows `pred` and `target` (h, w >= 1, any row stride >= 1, pixel stride >= 1).
+ * `pred_lut` / `target_lut` are 256 host bytes each: the class index (< classes) of a byte, or PG_LABEL_IGNORE.  For every pixel at which both
+ * sides map to a class, out[j][target class][predicted class] (int64 [npairs, classes, classes]) is incremented: `out` is ADDED to (integer
+ * atomics: exact, so order does not matter), the caller zeroes it -- or keeps a running count.  One launch.  PG_ERR_INVALID_ARG for npairs <= 0, a
+ * NULL pointer, h or w < 1, a stride < 1, classes outside 1..PG_CONFUSION_MAX_CLASSES or a look-up value >= classes other than PG_LABEL_IGNORE;
+ * PG_ERR_TOO_LARGE for h * w >= 2^31 or npairs > PG_METRIC_MAX_PAIRS. */
+#define PG_REGION_MAX 8
+#define PG_CONFUSION_MAX_CLASSES 16
+#define PG_LABEL_IGNORE 255
+typedef struct pg_region_pair {
+    const unsigned char* a;                /* first byte of window a */
+    const unsigned char* b;
+    const unsigned char* labels;           /* first byte of the label window */
+    int64_t a_row_stride;                  /* elements between rows */
+    int64_t b_row_stride;
+    int64_t l_row_stride;
+    int a_pix_stride;                      /* elements between pixels, >= channels */
+    int b_pix_stride;
+    int l_pix_stride;                      /* >= 1 */
+    int h, w, channels;
+} pg_region_pair;
+typedef struct pg_label_pair {
+    const unsigned char* pred;
+    const unsigned char* target;
+    int64_t p_row_stride;                  /* elements between rows */
+    int64_t t_row_stride;
+    int p_pix_stride;                      /* elements between pixels, >= 1 */
+    int t_pix_stride;
+    int h, w;
+} pg_label_pair;
+int64_t pg_region_pair_metrics_workspace(const pg_region_pair* jobs_host, int npairs, int nregions);
+int pg_region_pair_metrics_u8(const pg_region_pair* jobs_host, const pg_region_pair* jobs_device, int npairs, const uint32_t* regions, int nregions,
+                              void* workspace, int64_t* counts, double* ssim_sum, void* stream);
+int pg_label_confusion_u8(const pg_label_pair* jobs_host, const pg_label_pair* jobs_device, int npairs, const unsigned char* pred_lut,
+                          const unsigned char* target_lut, int classes, int64_t* out, void* stream);
+int pg_region_metrics_abi_version(void);
 
 #ifdef __cplusplus
 }

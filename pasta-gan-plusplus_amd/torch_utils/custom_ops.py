@@ -48,13 +48,14 @@ PLUGIN_SOURCES = {
     'snapshot_grid_plugin': ['snapshot_grid.hip'],
     'vgg_loss_plugin': ['vgg_loss.hip'],
     'image_metrics_plugin': ['image_metrics.hip'],
+    'region_metrics_plugin': ['region_metrics.hip'],
     'conv2d_plugin': ['conv2d.hip', 'conv2d_inst_k3s1.hip', 'conv2d_inst_k1s1.hip', 'conv2d_inst_k2x2.hip', 'conv2d_inst_k2x1.hip',
                       'conv2d_inst_k1x2.hip', 'conv2d_inst_k7s1.hip', 'conv2d_inst_k3s2.hip', 'conv2d_inst_k1s2.hip', 'conv2d_inst_wino.hip', 'conv2d_inst_wino4.hip', 'conv2d_inst_wino4s.hip', 'conv2d_inst_wino4t.hip', 'conv2d_inst_wino4x.hip', 'conv2d_inst_wino4xs.hip', 'conv2d_inst_wino4xt.hip', 'conv2d_inst_wino4b.hip', 'conv2d_inst_wino4bs.hip', 'conv2d_inst_up2.hip', 'conv2d_inst_stem7.hip', 'conv2d_inst_s2x3.hip', 'conv2d_inst_s1x1.hip',
                       'conv2d_wgrad.hip', 'conv2d16.hip', 'conv2d16_inst_k3s1.hip', 'conv2d16_inst_k3s1b.hip', 'conv2d16_inst_k1s1.hip', 'conv2d16_inst_k2x2.hip', 'conv2d16_inst_k2x1.hip',
                       'conv2d16_inst_k1x2.hip', 'conv2d16_inst_k3s2.hip', 'conv2d16_inst_up2f.hip', 'conv1x1_head16.hip', 'spade16.hip', 'conv1x1_fold.hip', 'conv3x3_fold.hip', 'optim.hip'],
 }
 
-ABI_VERSION = 21     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
+ABI_VERSION = 22     # == PG_ABI_VERSION of include/pasta_gan_ops.h; bumped with every struct / signature change
 
 _cached_plugins = dict()
 

@@ -99,6 +99,11 @@ def _finish(sad, ssd, ssim, count):
 
 def _ssim_cpu(a, b):
     """Mean SSIM of one pair of [h, w, C] uint8 CPU tensors, float64 (0-dim tensor)."""
+    return _ssim_map_cpu(a, b).mean()
+
+
+def _ssim_map_cpu(a, b):
+    """The SSIM map of one pair of [h, w, C] uint8 CPU tensors: float64 [C, 1, h - 10, w - 10]."""
     g = gaussian_taps()
     x = a.to(torch.float64).permute(2, 0, 1)[:, None]                # [C, 1, h, w]
     y = b.to(torch.float64).permute(2, 0, 1)[:, None]
@@ -108,7 +113,7 @@ def _ssim_cpu(a, b):
         return torch.nn.functional.conv2d(t, g.reshape(1, 1, WINDOW, 1))
     mx, my = blur(x), blur(y)
     vx, vy, cxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
-    return (((2 * mx * my + C1) * (2 * cxy + C2)) / ((mx * mx + my * my + C1) * (vx + vy + C2))).mean()
+    return ((2 * mx * my + C1) * (2 * cxy + C2)) / ((mx * mx + my * my + C1) * (vx + vy + C2))
 
 
 def _table_cpu(jobs):

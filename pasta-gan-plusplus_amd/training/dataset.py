@@ -158,6 +158,15 @@ def _garment_classes(parsing):
     return tops, dresses, pants, skirt
 
 
+def gt_parsing_classes(parsing):
+    """The 7-class ground-truth map of a raw parsing image (dataset.py:568-594 and the weighted sum after them): 0 other, 1 tops, 2 pants, 3 skirt,
+    4 dresses, 5 neck (label 10), 6 arms / legs (14-17) -> (gt_parsing in the sum's own dtype, the `_garment_classes` masks)."""
+    is_ = lambda *labels: np.isin(parsing, labels).astype(np.uint8)
+    hand_leg, neck = is_(14, 15, 16, 17), is_(10)
+    tops, dresses, pants, skirt = _garment_classes(parsing)
+    return tops * 1 + pants * 2 + skirt * 3 + dresses * 4 + neck * 5 + hand_leg * 6, (tops, dresses, pants, skirt)
+
+
 class TryOnTestSet(torch.utils.data.Dataset):
     """The reference's test sets: transfer the garment(s) of `clothes_name` onto `person_name`.
 
@@ -814,15 +823,13 @@ class TrainSet(torch.utils.data.Dataset):
 
         is_ = lambda *labels: np.isin(parsing, labels).astype(np.uint8)
         retain_mask = is_(18, 19) + self.palm_mask(kp, parsing) + is_(1, 2, 4, 13)             # shoes + palms + head
-        hand_leg, neck = is_(14, 15, 16, 17), is_(10)
         skin = is_(10, 13) * image
         medians = []
         for ch in range(3):
             vals = skin[..., ch].reshape(-1)
             vals = vals[vals > 0]
             medians.append(np.median(vals) if vals.size else np.nan)
-        tops, dresses, pants, skirt = _garment_classes(parsing)               # dataset.py:568-594: the same statements as the test classes'
-        gt_parsing = tops * 1 + pants * 2 + skirt * 3 + dresses * 4 + neck * 5 + hand_leg * 6
+        gt_parsing, (tops, dresses, pants, skirt) = gt_parsing_classes(parsing)               # (also calc_metrics.py's label windows)
         lower_mask, upper_mask = skirt + pants, tops + dresses
         upper_rgb, lower_rgb = np.repeat(upper_mask, 3, axis=2) * 255, np.repeat(lower_mask, 3, axis=2) * 255
 

@@ -217,7 +217,8 @@ def cell_sources(i, gnum):
 class SnapshotGrid:
     """What `setup_snapshot_grid` keeps (module docstring).  `canvases` uint8 [K, H, W, 3] with `upper_index` / `lower_index` [gnum^2] into it;
     `norm_img` [gnum^2, h, w, 30], `norm_img_lower` [gnum^2, h, w, 15], `bound` [gnum^2, H], `label` int32 [gnum^2]; `persons`: image, pose [gnum, H, W, 3],
-    retain_mask [gnum, H, W, 1], skin float32 [gnum, 3], label int32 [gnum], gt_rows / bound_test uint8 [gnum, H]; `person_index` [gnum^2]."""
+    retain_mask [gnum, H, W, 1], skin float32 [gnum, 3], label int32 [gnum], gt_rows / bound_test uint8 [gnum, H], gt_parsing uint8 [gnum, H, W, 1] (the
+    loader's 7-class map: the label windows of training/metrics.py); `person_index` [gnum^2]."""
 
     def __init__(self, gnum, device, persons, canvases, upper_index, lower_index, norm_img, norm_img_lower, bound, label, person_index):
         self.gnum, self.device, self.persons = gnum, device, persons
@@ -337,7 +338,7 @@ def setup_snapshot_grid(training_set, device, gnum=None):
             if ys.size:
                 gt_rows[i, ys[0]:] = 255
         persons = dict(image=up('image'), pose=up('pose'), retain_mask=up('retain_mask'), skin=up('skin'), label=up('label'),
-                       gt_rows=torch.from_numpy(gt_rows).to(dev), bound_test=up('bound_test'))
+                       gt_rows=torch.from_numpy(gt_rows).to(dev), bound_test=up('bound_test'), gt_parsing=up('gt_parsing'))
 
         cells = [cell_sources(i, g) for i in range(g * g)]
 

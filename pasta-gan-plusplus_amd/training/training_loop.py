@@ -10,7 +10,8 @@ Snapshots are plain ``torch.save`` dicts of ``state_dict``s under the reference'
 (training/vgg_loss.py); its tensors are buffers of the loss, in no snapshot.  Writing the reference's own pickle format is out of scope (its
 pickles embed module source), as are the contextual term, the reference's detector-based metrics (FID, KID, PR, PPL, IS), zip datasets and
 tensorboard.  ``metrics`` (``--metrics l1,psnr,ssim``) is opt-in: on image-snapshot ticks the reconstruction error of the grid's diagonal cells goes
-into ``stats.jsonl`` as ``Metric/recon_*`` (training/metrics.py)."""
+into ``stats.jsonl`` as ``Metric/recon_*`` (training/metrics.py); ``--metric-regions`` restricts it to label regions as well, and the name
+``parsing`` scores the parsing head (``Metric/parsing_*``)."""
 
 import argparse
 import json
@@ -98,13 +99,15 @@ def check_augment_options(aug, p, augpipe):
 
 def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, mask_weight=1.0, vgg_weight=0, contextual_weight=0, aug='ada', target=0.6,
                   seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None,
-                  vgg_ckpt=None, metrics=None, augpipe='bgc', p=None):
+                  vgg_ckpt=None, metrics=None, augpipe='bgc', p=None, metric_regions=None):
     """Train on the dataset directory `data` for `kimg` thousand images (one process, one GPU: `batch` = `batch_gpu` x accumulation rounds).
     Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied.
     `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none).
     `vgg_weight` > 0 turns the VGG19 perceptual term on and needs `vgg_ckpt` (no default path): NotImplementedError without one, FileNotFoundError for
     a path that does not exist, both before any network is built.  `metrics`: None, or names out of 'l1', 'psnr', 'ssim' -- each image-snapshot tick
-    then adds ``Metric/recon_<name>`` (training/metrics.py) to its ``stats.jsonl`` line and prints them after the status line.
+    then adds ``Metric/recon_<name>`` (training/metrics.py) to its ``stats.jsonl`` line and prints them after the status line -- and 'parsing':
+    ``Metric/parsing_acc`` / ``Metric/parsing_miou`` of the grid's predicted parsing.  `metric_regions`: None, or names out of ``metrics.REGIONS`` --
+    ``Metric/recon_<name>_<region>`` for each selected l1 / psnr / ssim (ValueError, before anything is built, when none of the three is selected).
     `aug`: 'ada' (adaptive, towards `target`), 'fixed' (the constant probability `p`, which also wins over a resumed snapshot's) or 'noaug'; `augpipe` names
     the pipeline out of ``augment.AUGPIPE_SPECS`` (reference train.py:259-305).  On a GPU the pipe's late stages run natively (``set_native_late``)."""
     if vgg_weight and vgg_ckpt is None:
@@ -115,6 +118,10 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
     if metrics:
         from . import metrics as metrics_mod
         metrics = metrics_mod.parse_metrics(metrics)
+    if metric_regions:
+        from . import metrics as metrics_mod
+        metric_regions = metrics_mod.parse_regions(metric_regions)
+        metrics_mod.check_region_options(metrics, metric_regions)
     if batch % batch_gpu:
         raise ValueError('--batch must be a multiple of --batch-gpu')
     check_augment_options(aug, p, augpipe)
@@ -186,7 +193,7 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
         rendered = None
         if metrics and image_tick:                                # the grid is rendered before the stats line is written: its figures go into it
             rendered = grid.render(G_ema, batch_gpu)
-            recon = metrics_mod.grid_reconstruction(grid, metrics)
+            recon = metrics_mod.grid_reconstruction(grid, metrics, metric_regions)
             means.update(recon)
             print(' '.join(f'{k} {v:.6g}' for k, v in recon.items()), flush=True)
         with open(os.path.join(run_dir, 'stats.jsonl'), 'a') as f:
@@ -231,7 +238,10 @@ def parse_args(argv=None):
     p.add_argument('--resume', help='a snapshot of this driver (.pt) or a reference network pickle (.pkl)')
     p.add_argument('--device', default='cuda')
     p.add_argument('--metrics', default='none', help="'none' or a comma-separated list out of l1, psnr, ssim: reconstruction error of the snapshot "
-                   "grid's diagonal cells on image-snapshot ticks (the reference's fid50k_full etc. need a detector network and are refused)")
+                   "grid's diagonal cells on image-snapshot ticks (the reference's fid50k_full etc. need a detector network and are refused); "
+                   "parsing: pixel accuracy and mean IoU of the grid's predicted parsing against the loader's gt_parsing")
+    p.add_argument('--metric-regions', default='none', help="'none' or a comma-separated list out of upper, lower, garment, skin, other: the selected "
+                   "l1 / psnr / ssim over these gt_parsing regions too (Metric/recon_<name>_<region>)")
     return p.parse_args(argv)
 
 
@@ -244,6 +254,14 @@ def main(argv=None):
             metrics = metrics_mod.parse_metrics(a.metrics)
         except ValueError as e:
             raise SystemExit(str(e))
+    regions = None
+    if a.metric_regions.strip().lower() not in ('', 'none'):
+        from . import metrics as metrics_mod
+        try:
+            regions = metrics_mod.parse_regions(a.metric_regions)
+            metrics_mod.check_region_options(metrics, regions)
+        except ValueError as e:
+            raise SystemExit(str(e))
     try:
         check_augment_options(a.aug, a.p, a.augpipe)
     except ValueError as e:
@@ -251,4 +269,4 @@ def main(argv=None):
     return training_loop(a.outdir, a.data, batch=a.batch, batch_gpu=a.batch_gpu, gamma=a.gamma, l1_weight=a.l1_weight, mask_weight=a.mask_weight,
                          vgg_weight=a.vgg_weight, contextual_weight=a.contextual_weight, aug=a.aug, target=a.target, seed=a.seed, workers=a.workers,
                          kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt, metrics=metrics,
-                         augpipe=a.augpipe, p=a.p)
+                         augpipe=a.augpipe, p=a.p, metric_regions=regions)
