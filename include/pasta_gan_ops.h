@@ -109,6 +109,9 @@ int pg_upfirdn2d_with_odd_samples(const void* x, const float* f, void* y, float*
                                   int fh, int fw, const int64_t fstride[2],
                                   int outH, int outW, const int64_t ystride[4],
                                   int padx0, int pady0, int flip, float gain, void* stream);
+/* Which kernel the last launch of this library went to: 1 = the 16-byte blur kernel (upfirdn2d_blur4), 2 = a tiled specialisation, 3 = a channels-last kernel,
+ * 4 = the generic kernel, 0 = none / declined.  For tests that assert a route; not synchronised with other host threads. */
+int pg_upfirdn2d_last_route(void);
 /* upfirdn2d followed, in the same pass, by the tail of a SynthesisLayer: v = fir(x) * gain + noise * noise_gain + bias[c];
  * y = clamp(act(v) * act_gain) with act in {linear, relu, lrelu}.  float32, dense NCHW, the filter sizes / factors of the
  * tiled kernel only (PG_ERR_UNSUPPORTED otherwise -- callers then run pg_upfirdn2d and pg_bias_act separately). */
@@ -212,6 +215,9 @@ int pg_conv2d_forward(const float* x, const float* packed_w, float* y,
  * pg_conv2d_splitk_plan returns the ksplit this library would choose (1 = use pg_conv2d_forward); not for spade_x / x2 launches.
  */
 int pg_conv2d_splitk_plan(int N, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride);
+/* Which kernel the last stride-1 1x1 launch of pg_conv2d_forward went to: 2 = the ring form of the streaming kernel, 1 = the streaming kernel,
+ * 0 = the tiled kernel (csrc/conv2d_s1x1.h).  For tests that assert a route; not synchronised with other host threads. */
+int pg_conv2d_last_1x1_route(void);
 int pg_conv2d_forward_splitk(const float* x, const float* packed_w, float* y,
                              int N, int Cin, int H, int W, int Cout, int KH, int KW,
                              int stride, int pad_y, int pad_x, int OH, int OW,
@@ -334,7 +340,8 @@ int pg_conv2d_stem7x3_forward(const float* x, const void* packed, float* y, int 
  * y [N, Cout, (H - 3) / 2 + 1, (W - 3) / 2 + 1] with strides ystride.  The arithmetic is pg_conv2d_up2x3_forward's: every float32 operand the exact sum of three
  * bf16 values (truncation split), a float32 product = the six largest of the nine plane products on v_mfma_f32_32x32x16_bf16, accumulated in float32, smallest
  * first.  The dropped products (each below 2^-24 of the product) and the behaviour on non-finite operands are as documented for conv2d_up2x3:
- * the split of +-inf leaves inf - inf = NaN in the second plane, so an infinite operand yields NaN where the fp32 kernel yields +-inf.
+ * the split of +-inf leaves inf - inf = NaN in the second plane, so an infinite operand yields NaN where the fp32 kernel yields +-inf.  A NaN sample stays
+ * local in the forward kernels that tests/test_nonfinite_locality.py lists: NaN in exactly the outputs that depend on it, -clamp under a fused clamp.
  * `packed_x3` = pg_conv2d_s2x3_pack_weight(packed) with `packed` = pg_conv2d_pack_weight of the OIHW 3x3 kernel; pg_conv2d_s2x3_packed_size(Cout, Cin) BYTES,
  * 16-byte aligned, once per weight version: [cout group of 128][16-channel chunk][m-block 4][tap 9][plane 3][k-half 2][32 couts][8 channels] bf16, zero
  * beyond Cout.  Serves Cin % 16 == 0, Cin >= 32, H, W >= 3, one image of x below 2^31 bytes.  x is read in whole aligned 16-byte words: of the memory outside

@@ -10,6 +10,8 @@
 //     v_mfma_f32_32x32x16_bf16 with the small products first (X3_PA / X3_PB): float32-class results at 6 / 16 of the fp32 MFMA's issue time.
 //   * non-finite operands: the unguarded split (x3_split, x3_split_pair) turns +-inf into inf - inf = NaN in the second plane, so an infinite operand yields
 //     NaN where an fp32 kernel yields +-inf; NaN stays NaN.  The guarded split (x3_split_guarded) keeps +-inf (and NaN) in the leading plane with zero remainders.
+//   * locality: a NaN sample reaches only the outputs that depend on it (tests/test_nonfinite_locality.py).  A kernel built on the split feeds
+//     the multiplier no sample outside its window: a K slot that exists only as padding holds a ZERO operand, not a real sample against a zero weight (0 x NaN).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -40,7 +40,7 @@ __device__ __forceinline__ S act_core(S x, S xr, S yy, S alpha) {
     const S selu_sa = (S)(1.0507009873554804934193349852946 * 1.6732632423543772848170429916717);
     if (A == PG_ACT_LINEAR) return G == 2 ? (S)0 : x;
     if (A == PG_ACT_RELU) {
-        if (G == 0) return x > 0 ? x : (S)0;
+        if (G == 0) return x <= 0 ? (S)0 : x;      // (a NaN stays NaN, as in torch.relu and in the fused tails' v * slope; every other x as x > 0 ? x : 0)
         if (G == 1) return yy > 0 ? x : (S)0;
         return (S)0;
     }
@@ -103,7 +103,7 @@ __device__ __forceinline__ T bias_act_one(T xv, T bv, T xrv, T yrv, T dyv, float
     if (G == 2) y *= (S)dyv;
     if (clamp >= (S)0) {
         if (G == 0) {
-            y = y > clamp ? clamp : (y < -clamp ? -clamp : y);
+            y = (y > -clamp && y < clamp) ? y : (y >= (S)0 ? clamp : -clamp);      // the plugin's select order: a NaN becomes -clamp, as in the fused tails (pg_common.h clamp_tail)
         } else {
             if (A == PG_ACT_SWISH) yr = swish_fwd<S, A>(xr) * gain;   // swish saves x, not y (bias_act.py:32)
             y = (yr > -clamp && yr < clamp) ? y : (S)0;

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256, PG_FOLD_MIN_WAVES) void conv1x1_fold_heads_ker
         wl[e] = o < Cout ? wn[o * C + c] : 0.f;
     }
     __syncthreads();
-    const float cl = clamp >= 0.f ? clamp : __builtin_inff();
+    const float cl = pg::clamp_bound(clamp);
     const f32x4s* xa = (const f32x4s*)x + (int64_t)n * C1 * HW4;
     const f32x4s* xb = (const f32x4s*)x2 + (int64_t)n * C2 * HW4;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < HW4; p += (int64_t)gridDim.x * 256) {

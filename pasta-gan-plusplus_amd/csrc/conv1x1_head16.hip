@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void conv1x1_head16_kernel(const unsigned shor
     float bo[COUT];
 #pragma unroll
     for (int o = 0; o < COUT; o++) bo[o] = bias ? bias[o] : 0.f;
-    const float cl = clamp >= 0.f ? clamp : __builtin_inff();
+    const float cl = pg::clamp_bound(clamp);
     const unsigned short* xn = x + (int64_t)n * HW * Cin;
     const int npass = (HW + PB - 1) / PB;
     const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;

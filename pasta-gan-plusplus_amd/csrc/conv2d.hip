@@ -534,7 +534,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
                                                             int osy, int osx, int ooy, int oox, pg_conv2d_fusion f) {
     const int64_t total = (int64_t)N * Cout * OH * OW;
     const float slope = f.act == PG_ACT_LINEAR ? 1.f : (f.act == PG_ACT_RELU ? 0.f : f.alpha);
-    const float cl = f.clamp >= 0.f ? f.clamp : __builtin_inff();
+    const float cl = clamp_bound(f.clamp);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int ox = (int)(i % OW), oy = (int)((i / OW) % OH), co = (int)((i / ((int64_t)OW * OH)) % Cout), n = (int)(i / ((int64_t)OW * OH * Cout));
         float v = 0.f;
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
         if (f.noise) v += f.noise[n * f.noise_batch_stride + (int64_t)oy * OW + ox] * f.noise_gain;
         if (f.bias) v += f.bias[co];
         v = v > 0.f ? v : v * slope;
-        v = fminf(fmaxf(v * f.gain, -cl), cl);
+        v = clamp_tail(v * f.gain, cl);
         const int64_t off = n * ys0 + co * ys1 + (int64_t)(oy * osy + ooy) * ys2 + (int64_t)(ox * osx + oox) * ys3;
         if (f.residual) v += f.residual[off];
         y[off] = v;
@@ -683,6 +683,8 @@ PG_EXPORT int pg_conv2d_forward(const float* x, const float* packed_w, float* y,
                         ystride, out_step_y, out_step_x, out_off_y, out_off_x, fusion, stream);
 }
 
+PG_EXPORT int pg_conv2d_last_1x1_route(void) { return pgconv::last_1x1_route(); }
+
 PG_EXPORT int pg_conv2d_splitk_plan(int N, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride) {
     if (N <= 0 || Cin <= 0 || OH <= 0 || OW <= 0 || Cout <= 0) return 1;
     if (!((stride == 1 && ((KH == 3 && KW == 3) || (KH == 1 && KW == 1) || (KH == 2 && KW == 2) || (KH == 2 && KW == 1) || (KH == 1 && KW == 2) || (KH == 7 && KW == 7))) ||
@@ -757,7 +759,7 @@ __global__ __launch_bounds__(256) void conv1x1_small_f32_kernel(const float* __r
         wl[e] = o < COUT ? w[o * Cin + c] * scale * (styles ? styles[(int64_t)n * Cin + c] : 1.f) : 0.f;
     }
     __syncthreads();
-    const float cl = clamp >= 0.f ? clamp : __builtin_inff();
+    const float cl = pg::clamp_bound(clamp);
     const f32x4s* xn = (const f32x4s*)x + (int64_t)n * Cin * HW4;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < HW4; p += (int64_t)gridDim.x * 256) {
         f32x4s acc[COUT];
@@ -840,7 +842,7 @@ __global__ __launch_bounds__(256) void conv1x1_small_f32_split_kernel(const floa
 #pragma unroll 8
         for (int z = 1; z < CS; z++) r += part[z][o][oq];
         r += bias ? bias[o] : 0.f;
-        const float cl = clamp >= 0.f ? clamp : __builtin_inff();
+        const float cl = pg::clamp_bound(clamp);
 #pragma unroll
         for (int e = 0; e < 4; e++) r[e] = fminf(fmaxf(r[e], -cl), cl);
         if (po < HW4) {

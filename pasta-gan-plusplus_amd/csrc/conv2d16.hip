@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void splitk_finish16_kernel(const float* __res
                                                               int osy, int osx, int ooy, int oox, pg_conv2d16_fusion f) {
     const int64_t total = (int64_t)N * Cout * OH * OW;
     const float slope = f.act == PG_ACT_LINEAR ? 1.f : (f.act == PG_ACT_RELU ? 0.f : f.alpha);
-    const float cl = f.clamp >= 0.f ? f.clamp : __builtin_inff();
+    const float cl = clamp_bound(f.clamp);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int cot = (int)(i % Cout), ox = (int)((i / Cout) % OW), oy = (int)((i / ((int64_t)Cout * OW)) % OH), n = (int)(i / ((int64_t)Cout * OW * OH));
         const int pc = f.phase_cout, ph = pc ? cot / pc : 0, co = cot - ph * pc, ce = pc ? pc : Cout;      // four-phase mode: pg_conv2d16_fusion
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void splitk_finish16_kernel(const float* __res
         if (f.noise) v += f.noise[n * f.noise_batch_stride + ph * f.noise_phase_stride + (int64_t)oy * OW + ox] * f.noise_gain;
         if (f.bias) v += f.bias[co];
         v = v > 0.f ? v : v * slope;
-        v = fminf(fmaxf(v * f.gain, -cl), cl);
+        v = clamp_tail(v * f.gain, cl);
         const int64_t off = n * ys0 + co * ys1 + (int64_t)(oy * osy + (pc ? (ph >> 1) : ooy)) * ys2 + (int64_t)(ox * osx + (pc ? (ph & 1) : oox)) * ys3;
         if (out_f32) {
             if (f.residual) v += ((const float*)f.residual)[off];
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void splitk_finish16_vec4_kernel(const float* 
                                                                    int total4, int Cout, int OH, int OW, int64_t ys0, int64_t ys2, int64_t ys3,
                                                                    int osy, int osx, int ooy, int oox, pg_conv2d16_fusion f) {
     const float slope = f.act == PG_ACT_LINEAR ? 1.f : (f.act == PG_ACT_RELU ? 0.f : f.alpha);
-    const float cl = f.clamp >= 0.f ? f.clamp : __builtin_inff();
+    const float cl = clamp_bound(f.clamp);
     const int Cout4 = Cout >> 2;
     for (int q = blockIdx.x * 256 + threadIdx.x; q < total4; q += gridDim.x * 256) {
         const int c4 = q % Cout4;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void splitk_finish16_vec4_kernel(const float* 
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const float a = v[j] > 0.f ? v[j] : v[j] * slope;
-            v[j] = fminf(fmaxf(a * f.gain, -cl), cl);
+            v[j] = clamp_tail(a * f.gain, cl);
         }
         const int64_t off = n * ys0 + co + (int64_t)(oy * osy + (pc ? (ph >> 1) : ooy)) * ys2 + (int64_t)(ox * osx + (pc ? (ph & 1) : oox)) * ys3;
         if (f.residual) {
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void conv1x1_small16_kernel(const unsigned sho
         wl[e] = w[e] * (styles ? styles[(int64_t)n * Cin + c] : 1.f);
     }
     __syncthreads();
-    const float cl = clamp >= 0.f ? clamp : __builtin_inff();
+    const float cl = pg::clamp_bound(clamp);
     const unsigned short* xn = x + (int64_t)n * HW * Cin;
     const int sub = threadIdx.x % LP;
     constexpr int PPB = 256 / LP;                                     // pixels per block and pass

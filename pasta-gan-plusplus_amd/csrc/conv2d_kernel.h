@@ -263,6 +263,7 @@ __global__ __launch_bounds__(256, (Geo<KH, KW, S, BM, KC>::MIN_BLOCKS)) void con
 #pragma unroll
                     for (int nt = 0; nt < G::NT; nt++) {
                         float v = b_base[(2 * cp) * G::PLANE + (nt * S + ky) * G::IW_T + kx];
+                        if constexpr (ROWPAIR) { if (ky == KH - 1 && half && p.rowpair && c0 == 2) v = 0.f; }      // the last row has no pair (its weight is zero, but 0 x NaN is NaN): the sample a row below the window stays out
                         if (MODE != 0) v *= sc;
                         if (XF) v = __builtin_amdgcn_fmed3f(fmaxf(v, v * in_slope), -in_cl, in_cl);
                         b[nt] = v;
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(256, (Geo<KH, KW, S, BM, KC>::MIN_BLOCKS)) void con
     };
 
     const float gain = p.f.gain;
-    const float cl = p.f.clamp >= 0.f ? p.f.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.f.clamp);
     const float slope = act_slope(p.f.act, p.f.alpha);
     const bool plain_tail = !p.f.noise && slope == 1.f && gain == 1.f && p.f.clamp < 0.f;      // wave-uniform
 
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(256, (Geo<KH, KW, S, BM, KC>::MIN_BLOCKS)) void con
                     for (int j = 0; j < 4; j++) {
                         float v = (ex[j] - mu4[j]) * rs4[j] * (1.f + acc[0][nt][4 * kq + j]) + acc[G::MT - 1][nt][4 * kq + j];
                         v = v > 0.f ? v : v * slope;                 // the consumer's pre-activation (Spade_Conv2dLayer), when folded in
-                        v = fminf(fmaxf(v * gain, -cl), cl);
+                        v = clamp_tail(v * gain, cl);
                         if (pix_ok[nt]) p.y[o + j * cstride] = v;
                     }
                 }
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(256, (Geo<KH, KW, S, BM, KC>::MIN_BLOCKS)) void con
                     for (int j = 0; j < 4; j++) {
                         float v = acc[mt][nt][4 * kq + j] * sc4[j] + nz[nt] + bi4[j];
                         v = v > 0.f ? v : v * slope;
-                        v = fminf(fmaxf(v * gain, -cl), cl) + ex[j];
+                        v = clamp_tail(v * gain, cl) + ex[j];
                         if ((DIRECT_EXP & 1) ? (v == 12345.678f) : (pix_ok[nt] && e_m0 + row0 + j < p.Cout)) p.y[o + j * cstride] = v;
                     }
                 }
@@ -501,6 +502,7 @@ int launch_wino(const ConvParams& p, hipStream_t s);     // conv2d_wino.h
 int launch_wino4b(const ConvParams& p, hipStream_t s);   // conv2d_wino4b.h: F(4x4,3x3), two workgroups per CU (16x16x4 MFMA); PG_ERR_UNSUPPORTED when the launch is not its kind
 int launch_wino4(const ConvParams& p, hipStream_t s);    // conv2d_wino4.h: F(4x4,3x3); PG_ERR_UNSUPPORTED when the launch is not its kind
 int launch_wino4x3(const ConvParams& p, hipStream_t s);  // conv2d_wino4.h, X3 form: the transform-domain GEMM on the bf16 pipe (three-term operand splits); same acceptance as launch_wino4
+int last_1x1_route();                                    // conv2d_inst_s1x1.hip: where the last launch_s1x1 call went
 int launch_s1x1(const ConvParams& p, hipStream_t s);     // conv2d_s1x1.h: streaming 1x1 (returns PG_ERR_UNSUPPORTED when the launch is not its kind)
 
 }  // namespace pgconv

@@ -433,7 +433,7 @@ __global__ __launch_bounds__(SPLIT ? THREADS + 64 * LOADERS : THREADS, SPLIT ? 3
     };
 
     const float gain = p.f.gain;
-    const float cl = p.f.clamp >= 0.f ? p.f.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.f.clamp);
     const float slope = act_slope(p.f.act, p.f.alpha);
     const bool has_scale = p.f.out_scale != nullptr;
     const float noise_gain = p.f.noise ? p.f.noise_gain : 0.f;
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(SPLIT ? THREADS + 64 * LOADERS : THREADS, SPLIT ? 3
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         const float u = fmaf(acc[mt][nt][4 * g + j], sgv[j], bgv[j] + nz);
-                        v[4 * g + j] = __builtin_amdgcn_fmed3f(fmaxf(u, u * slope), -cl, cl);
+                        v[4 * g + j] = clamp_tail_med3(fmaxf(u, u * slope), cl);
                     }
                 }
                 if (p.out_mode == OUT_VEC16) {

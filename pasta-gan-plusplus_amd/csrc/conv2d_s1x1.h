@@ -41,7 +41,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_stream(ConvParams p) {
     const int ptiles = (int)((HW + WPIX * WAVES - 1) / (WPIX * WAVES));
     const int split = p.f.x2 ? p.f.cin_split : p.Cin;
     const float gain = p.f.gain, slope = act_slope(p.f.act, p.f.alpha);
-    const float cl = p.f.clamp >= 0.f ? p.f.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.f.clamp);
     const bool plain_tail = slope == 1.f && gain == 1.f && p.f.clamp < 0.f;
 
     int cur_key = -1;
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_stream(ConvParams p) {
 #pragma unroll
                         for (int e = 0; e < E; e++) {
                             float r = fmaf(acc[mt][e][k], sc, bi);
-                            if (!plain_tail) { r = r > 0.f ? r : r * slope; r = fminf(fmaxf(r * gain, -cl), cl); }
+                            if (!plain_tail) { r = r > 0.f ? r : r * slope; r = clamp_tail(r * gain, cl); }
                             v[e] = r;
                         }
                         if (rb) v += *(const vec_t*)(rb + (int64_t)co * p.ys[1]);
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_stream_ring(ConvParams p) {
     const int split = p.f.x2 ? p.f.cin_split : p.Cin;
     const int ngroups = p.Cin / (2 * GRP);
     const float gain = p.f.gain, slope = act_slope(p.f.act, p.f.alpha);
-    const float cl = p.f.clamp >= 0.f ? p.f.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.f.clamp);
     const bool plain_tail = slope == 1.f && gain == 1.f && p.f.clamp < 0.f;
 
     typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_stream_ring(ConvParams p) {
 #pragma unroll
                 for (int e = 0; e < E; e++) {
                     float r = fmaf(acc[mt][e][k], sc, bi);
-                    if (!plain_tail) { r = r > 0.f ? r : r * slope; r = fminf(fmaxf(r * gain, -cl), cl); }
+                    if (!plain_tail) { r = r > 0.f ? r : r * slope; r = clamp_tail(r * gain, cl); }
                     v[e] = r;
                 }
                 float* dst = yb + (int64_t)(m0 + row) * p.ys[1];

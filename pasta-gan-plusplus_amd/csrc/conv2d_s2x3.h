@@ -229,7 +229,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
     }
     unsigned long long st_mm = 0, st_bar = 0, st_ep = 0, st_t0 = 0, st_rounds = 0;      // (SX_EXP & 32: cycle totals of this wave)
     const float gain = p.gain;
-    const float cl = p.clamp >= 0.f ? p.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.clamp);
     const float slope = act_slope(p.act, p.alpha);
     const int cs_ = (int)p.ys[1], rs_ = (int)p.ys[2], xs_ = (int)p.ys[3];
     asm volatile("s_barrier" ::: "memory");                           // barrier 0: the producers have made chunk 0
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_s2x3(S2x3Params p) {
                     for (int j = 0; j < 4; j++) {
                         float v = (acc[a][4 * kq + j] + accs[a][4 * kq + j]) + b4[j];
                         v = v > 0.f ? v : v * slope;
-                        v = fminf(fmaxf(v * gain, -cl), cl);
+                        v = clamp_tail(v * gain, cl);
                         const unsigned off = (ok && co0 + 8 * kq + j < p.Cout && (!(SX_EXP & 16) || v == 12345.678f)) ? o0 + (unsigned)(j * cs_) * 4u : 0x80000000u;      // out of range: dropped
                         asm volatile("buffer_store_dword %0, %1, %2, 0 offen" :: "v"(v), "v"(off), "s"(yrsrc) : "memory");
                     }

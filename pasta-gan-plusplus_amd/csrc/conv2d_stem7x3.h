@@ -2,12 +2,14 @@
 // with its multiplies on the bf16 matrix pipe (round 6) in the three-term arithmetic of bf16x3.h (the six products in this kernel's own order, PA6 / PB6 below).
 // The layer is 39.5 GFLOP at N = 8, 512^2: 251 us at the fp32 matrix peak, 452 us measured on conv2d_mfma<7,7,1,64,2,0>; its output is 537 MB (~110 us of HBM).
 //
-//   * K order = (kx, ci, ky): 21 groups of 8 (seven rows ky + one zero weight), 168 -> 11 MFMA K steps (the last half step all zero).  A lane's B operand of a
-//     group is then 8 VERTICALLY consecutive samples of one input column and channel -- a "column record": 16 bytes, the same for every pixel of an output row
+//   * K order = (kx, ci, ky): 21 groups of 8 (seven rows ky + one zero weight against a zero operand), 168 -> 11 MFMA K steps (the last half step all zero, operands too).  A lane's B operand of a
+//     group is then 7 VERTICALLY consecutive samples (and a zero) of one input column and channel -- a "column record": 16 bytes, the same for every pixel of an output row
 //     that uses the column, 16-byte aligned whatever the pixel's x (a horizontal window would start at any 2-byte offset).
 //   * workgroup = 8 waves = a vertical strip of 256 output columns x 32 rows x 64 couts, walked row by row.  LDS holds the records of the current row
 //     [plane 3][channel 3][262 columns] x 16 B, double buffered.  While the row is multiplied, the threads make the next row's records (786 (channel, column) tasks, at most two per thread): read the
-//     task's three plane records, shift them down one sample (v_alignbit), insert the split of the sample five rows below (requested a row ahead) -- one barrier per row.
+//     task's three plane records, shift them down one sample (v_alignbit), insert the split of the sample four rows below (requested at the top of the row) --
+//     one barrier per row.  The 8th slot of a record stays zero and the 22nd half step reads all-zero records: no sample outside the 7x7 window meets a
+//     multiplier (0 x NaN is NaN: it would spread to a row the window never touches).
 //     Every input sample is split once per strip and row: ~60 VALU per lane and row beside 132 MFMAs per wave and row.
 //   * the weights (64 couts x 176 x three planes) never leave registers: wave = (m-tile of 32 couts, two of the eight 32-pixel blocks of the row), its 33 A
 //     fragments (132 registers) are loaded once per launch.  Two accumulators per wave; two waves per SIMD.
@@ -24,6 +26,7 @@ namespace pgconv {
 
 constexpr int S7_TW = 256, S7_NCOL = S7_TW + 6, S7_ROWS = 32, S7_KS = 11, S7_GROUPS = 21;      // S7_ROWS: rows of a segment at most (the launcher halves it while the grid does not fill the chip)
 constexpr int S7_REC_B = 9 * S7_NCOL * 16;                   // bytes of one buffer of records
+constexpr int S7_ZERO_B = (2 * 3 * S7_NCOL + 128 + 1) * 16;  // bytes of the all-zero records: every offset a B-operand load adds to its base lands inside
 
 struct Stem7Params {
     const float* x; float* y; const unsigned char* wx3; const float* bias;
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
             for (int pl = 0; pl < 3; pl++) A[ks][pl] = *(const x3_u32x4*)(wb + (size_t)(ks * 3 + pl) * 64 * 16);
     }
 
-    // ---- records of row y0: rows y0 - 3 .. y0 + 4.  A record task = (channel, column): 3 x 262 = 786 of them, at most two per thread (task = tid, tid + 512;
+    // ---- records of row y0: rows y0 - 3 .. y0 + 3, the 8th slot zero (its weight is zero, but 0 x NaN is NaN: no sample below the window goes in).  A record task = (channel, column): 3 x 262 = 786 of them, at most two per thread (task = tid, tid + 512;
     // consecutive threads take consecutive columns: coalesced sample loads)
     int rec_off[2];                                           // byte offset of the task's plane-0 record in a buffer, < 0: no task
     unsigned voff[2];                                         // byte offset of the task's column in row 0 of its channel (0x80000000: outside the image -> zero)
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
         if (rec_off[q] >= 0) {
             x3_u32x4 r[3] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
+            for (int j = 0; j < 7; j++) {
                 const int row = y0 - 3 + j;
                 const float v = (voff[q] != 0x80000000u && row >= 0 && row < p.H) ? xin[(voff[q] >> 2) + row * p.W] : 0.f;
                 unsigned b0, b1, b2;
@@ -92,6 +95,9 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
     }
     float* smp_s = (float*)(s7_smem + 2 * S7_REC_B);          // [2 tasks][512 threads] samples of the row being inserted (LDS-DMA)
     float* bias_s = smp_s + 2 * 512;                          // [64]
+    // zero records: what the lanes of the 22nd half step read.  That half step has no group: its weights are zero, and so must its operands be (0 x NaN is NaN)
+    const unsigned char* zero_s = (const unsigned char*)(bias_s + 64);
+    for (int i = tid; i < S7_ZERO_B / 16; i += 512) *(x3_u32x4*)(s7_smem + (size_t)(2 * S7_REC_B + (2 * 512 + 64) * 4) + (size_t)i * 16) = x3_u32x4{0u, 0u, 0u, 0u};
     if (tid < 64) {
         const int co = mp * 64 + tid;
         bias_s[tid] = (p.bias && co < p.Cout) ? p.bias[co] : 0.f;
@@ -124,19 +130,19 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
     }
 
     const float gain = p.gain;
-    const float cl = p.clamp >= 0.f ? p.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.clamp);
     const float slope = act_slope(p.act, p.alpha);
 
     for (int yy = y0; yy < y1; yy++) {
         const int buf = (yy - y0) & 1;
         const unsigned char* cur = s7_smem + (size_t)buf * S7_REC_B;
         unsigned char* nb = s7_smem + (size_t)(buf ^ 1) * S7_REC_B;
-        // ---- the next row's records (rows yy - 2 .. yy + 5): the samples of row yy + 5 go straight to LDS (LDS-DMA from inline asm, waited for by hand after
+        // ---- the next row's records (rows yy - 2 .. yy + 4): the samples of row yy + 4 go straight to LDS (LDS-DMA from inline asm, waited for by hand after
         // K step 7).  A load the compiler can see would make it wait -- `s_waitcnt vmcnt(0)` at the top of the loop -- for the previous row's output stores as well.
         const bool upd = yy + 1 < y1 && !(S7_EXP & 1);
         if (upd) {
-            const bool row_ok = yy + 5 < p.H;                 // (yy + 5 >= 0 always)
-            const int soff = row_ok ? (yy + 5) * p.W * 4 : 0;
+            const bool row_ok = yy + 4 < p.H;                 // (yy + 4 >= 0 always)
+            const int soff = row_ok ? (yy + 4) * p.W * 4 : 0;
 #pragma unroll
             for (int q = 0; q < 2; q++) dma_dword(xrsrc, smp_b + 2048u * q, row_ok ? voff[q] : 0x80000000u, soff);
         }
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
                         o[0] = __builtin_amdgcn_alignbit(r[1], r[0], 16);
                         o[1] = __builtin_amdgcn_alignbit(r[2], r[1], 16);
                         o[2] = __builtin_amdgcn_alignbit(r[3], r[2], 16);
-                        o[3] = __builtin_amdgcn_alignbit(b[pl], r[3], 16);
+                        o[3] = b[pl];                         // slot 6 = the new sample, slot 7 = 0
                         *(x3_u32x4*)(nb + ro) = o;
                     }
                 }
@@ -171,8 +177,9 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
         // B operands: plane 0 of a K step is requested one step ahead and its three products go first, so planes 1 and 2 -- requested at the top of the step --
         // arrive behind 6 MFMAs (two waves per SIMD and 132 registers of weights leave no room for a whole step of look-ahead: 134 us of exposed LDS latency)
         auto b_addr = [&](int ks) __attribute__((always_inline)) {
-            const int g0 = 2 * ks, g1 = 2 * ks + 1 < S7_GROUPS ? 2 * ks + 1 : S7_GROUPS - 1;      // group = 3 kx + ci (the 22nd half step has zero weights: any record)
+            const int g0 = 2 * ks, g1 = 2 * ks + 1;                                                // group = 3 kx + ci
             const int off0 = ((g0 % 3) * S7_NCOL + g0 / 3) * 16, off1 = ((g1 % 3) * S7_NCOL + g1 / 3) * 16;
+            if (g1 >= S7_GROUPS) return half ? zero_s : cur + off0 + (size_t)(32 * bq + l31) * 16;      // the 22nd half step: the zero records (one address select per row)
             return cur + (half ? off1 : off0) + (size_t)(32 * bq + l31) * 16;
         };
         auto b_load = [&](const unsigned char* bb, int pl, int bi) __attribute__((always_inline)) {
@@ -218,7 +225,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_stem7x3(Stem7Params p) {
                 const int rowc = (k & 3) + 8 * (k >> 2);
                 float v = acc[bi][k] + bias_s[mt * 32 + 4 * half + rowc];
                 v = v > 0.f ? v : v * slope;
-                v = fminf(fmaxf(v * gain, -cl), cl);
+                v = clamp_tail(v * gain, cl);
                 const unsigned off = (px < p.W && co0 + rowc < p.Cout && (!(S7_EXP & 2) || v == 12345.678f)) ? o0 + (unsigned)(rowc * (int)p.ys[1]) * 4u : 0x80000000u;      // out of range: dropped
                 asm volatile("buffer_store_dword %0, %1, %2, %3 offen" :: "v"(v), "v"(off), "s"(yrsrc), "s"(row_soff));
             }
@@ -253,7 +260,7 @@ inline int launch_stem7x3(Stem7Params p, hipStream_t s) {
     const int64_t blocks = (int64_t)p.N * p.mpairs * p.strips * p.segs;
     if (blocks > 0x7fffffffLL || (int64_t)3 * p.H * p.W >= 0x7fffffffLL) return PG_ERR_TOO_LARGE;
     if (((int64_t)(p.mpairs * 64) * p.ys[1] + (int64_t)p.H * p.ys[2] + (int64_t)p.W * p.ys[3]) * 4 >= 0x7fffffffLL) return PG_ERR_UNSUPPORTED;      // 32-bit byte offsets inside one image of y
-    const size_t lds = (size_t)2 * S7_REC_B + (2 * 512 + 64) * sizeof(float);
+    const size_t lds = (size_t)2 * S7_REC_B + (2 * 512 + 64) * sizeof(float) + S7_ZERO_B;
     static PerDeviceOnce once;
     const hipError_t e = once.run([] { return hipFuncSetAttribute((const void*)conv2d_stem7x3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     if (e != hipSuccess) return (int)e;

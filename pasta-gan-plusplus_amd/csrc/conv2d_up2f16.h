@@ -259,7 +259,7 @@ __global__ __launch_bounds__((MW + MW / 2) * 64, 3) void conv2d_up2f16(Up2fParam
     // u = h * (scale * gain) + (bias + noise) * gain, v = med3(max(u, u * slope), -cl, cl).  Without a per-cout scale (per-sample weight packs carry the
     // demodulation) the gain rides in the filter taps and the bias + noise term is the filter sum's start value: 4 multiply-adds + 1 add per value.
     const float gain = p.f.gain;
-    const float cl = p.f.clamp >= 0.f ? p.f.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.f.clamp);
     const float slope = act_slope(p.f.act, p.f.alpha);
     const bool has_scale = p.f.out_scale != nullptr;
     const float ng = (p.f.noise ? p.f.noise_gain : 0.f) * gain;
@@ -317,8 +317,8 @@ __global__ __launch_bounds__((MW + MW / 2) * 64, 3) void conv2d_up2f16(Up2fParam
                             }
                         }
                         if (dbg_ & 64) { ve[j] = ue; vo[j] = uo; continue; }
-                        ve[j] = __builtin_amdgcn_fmed3f(fmaxf(ue, ue * slope), -cl, cl);
-                        vo[j] = __builtin_amdgcn_fmed3f(fmaxf(uo, uo * slope), -cl, cl);
+                        ve[j] = clamp_tail_med3(fmaxf(ue, ue * slope), cl);
+                        vo[j] = clamp_tail_med3(fmaxf(uo, uo * slope), cl);
                     }
                     u32x2 ce = {HT::pack(ve[0], ve[1]), HT::pack(ve[2], ve[3])}, co2 = {HT::pack(vo[0], vo[1]), HT::pack(vo[2], vo[3])};
                     if (g & 1) {
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(Up2pGeo::NTHREADS, 2) void conv2d_up2f16p(Up2fParam
     // ---------------------------------------------------------------- serving role, part 2: the epilogue of this group's previous tile, in blocks
     //   u = h * (scale * gain) + (bias + noise) * gain,  v = med3(max(u, u * slope), -cl, cl)  (positively homogeneous activations, gain > 0)
     const float gain = p.f.gain;
-    const float cl = p.f.clamp >= 0.f ? p.f.clamp : __builtin_inff();
+    const float cl = clamp_bound(p.f.clamp);
     const float slope = act_slope(p.f.act, p.f.alpha);
     const bool has_scale = p.f.out_scale != nullptr;
     const float ng = (p.f.noise ? p.f.noise_gain : 0.f) * gain;
@@ -640,8 +640,8 @@ __global__ __launch_bounds__(Up2pGeo::NTHREADS, 2) void conv2d_up2f16p(Up2fParam
             const float ho = fmaf(f3, z0[j], fmaf(f2, z1[j], fmaf(f1, z0p, f0 * z1p)));
             // (taps carry the gain when there is no per-cout scale: sgv == 1 then -- one code path)
             const float ue = fmaf(he, has_scale ? sgv[j] : 1.f, bgv[j] + nze), uo = fmaf(ho, has_scale ? sgv[j] : 1.f, bgv[j] + nzo);
-            ve[j] = __builtin_amdgcn_fmed3f(fmaxf(ue, ue * slope), -cl, cl);
-            vo[j] = __builtin_amdgcn_fmed3f(fmaxf(uo, uo * slope), -cl, cl);
+            ve[j] = clamp_tail_med3(fmaxf(ue, ue * slope), cl);
+            vo[j] = clamp_tail_med3(fmaxf(uo, uo * slope), cl);
         }
         u32x2 ce = {HT::pack(ve[0], ve[1]), HT::pack(ve[2], ve[3])}, co2 = {HT::pack(vo[0], vo[1]), HT::pack(vo[2], vo[3])};
         if (g & 1) {

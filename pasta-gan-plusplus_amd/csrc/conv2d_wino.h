@@ -402,7 +402,7 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino(ConvParams p) {
         const int oy = e_oy0 + prow, ox = e_ox0 + 2 * tcol;
         const bool spade = q.f.spade_x != nullptr;
         const float gain = q.f.gain, slope = act_slope(q.f.act, q.f.alpha);
-        const float cl = q.f.clamp >= 0.f ? q.f.clamp : __builtin_inff();
+        const float cl = clamp_bound(q.f.clamp);
         const bool vec_store = q.ys[3] == 1 && ((q.ys[0] | q.ys[1] | q.ys[2]) & 1) == 0 && (((uintptr_t)q.y) & 7) == 0 && (q.OW & 1) == 0;
         const bool full = vec_store && e_oy0 + 2 <= q.OH && e_ox0 + 64 <= q.OW && e_m0 + 64 <= q.Cout;      // wave-uniform
         const bool row_ok = oy < q.OH;
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino(ConvParams p) {
                 f32x2 v = (r0 - mu) * rs * (yv[0] + 1.f) + yv[1];
                 if (!plain_tail) {                                           // the consumer's pre-activation (Spade_Conv2dLayer) folded in
 #pragma unroll
-                    for (int e = 0; e < 2; e++) v[e] = __builtin_amdgcn_fmed3f((v[e] > 0.f ? v[e] : v[e] * slope) * gain, -cl, cl);
+                    for (int e = 0; e < 2; e++) v[e] = clamp_tail_med3((v[e] > 0.f ? v[e] : v[e] * slope) * gain, cl);
                 }
                 store2(pix0_b + (unsigned)((e_m0 >> 1) + chl) * cstride_b, v, true);
             } else {
@@ -504,7 +504,7 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino(ConvParams p) {
                     f32x2 v = yv[kk] * esc + (nz + ebi);
                     if (!plain_tail) {
 #pragma unroll
-                        for (int e = 0; e < 2; e++) v[e] = __builtin_amdgcn_fmed3f((v[e] > 0.f ? v[e] : v[e] * slope) * gain, -cl, cl);
+                        for (int e = 0; e < 2; e++) v[e] = clamp_tail_med3((v[e] > 0.f ? v[e] : v[e] * slope) * gain, cl);
                     }
                     v += kk ? r1 : r0;
                     store2(pix0_b + (unsigned)((full || co < q.Cout) ? co : q.Cout - 1) * cstride_b, v, co < q.Cout);

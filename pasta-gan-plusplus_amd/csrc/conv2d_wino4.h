@@ -576,7 +576,7 @@ __global__ __launch_bounds__(768, 3) void conv2d_wino4(ConvParams p) {
         const auto& qa = *fresh_args();
         const bool spade = TAIL == W4_TAIL_SPADE ? true : (TAIL == W4_TAIL_ANY ? qa.f.spade_x != nullptr : false);
         const float gain = qa.f.gain, slope = act_slope(qa.f.act, qa.f.alpha);
-        const float cl = qa.f.clamp >= 0.f ? qa.f.clamp : __builtin_inff();
+        const float cl = clamp_bound(qa.f.clamp);
         const bool plain_tail = slope == 1.f && gain == 1.f && qa.f.clamp < 0.f;
         const int OHv = qa.OH, OWv = qa.OW, Coutv = qa.Cout;
         const float ngain = qa.f.noise_gain * (spade ? 1.f : gain);      // (gain folded: see the epilogue constants)
@@ -598,7 +598,7 @@ __global__ __launch_bounds__(768, 3) void conv2d_wino4(ConvParams p) {
         auto act4 = [&](f32x4 v) {                                       // SPADE tail: the gain cannot ride in per-cout constants there
             if (!plain_tail) {
 #pragma unroll
-                for (int e = 0; e < 4; e++) v[e] = __builtin_amdgcn_fmed3f(fmaxf(v[e] * g_pos, v[e] * g_neg), -cl, cl);
+                for (int e = 0; e < 4; e++) v[e] = clamp_tail_med3(fmaxf(v[e] * g_pos, v[e] * g_neg), cl);
             }
             return v;
         };

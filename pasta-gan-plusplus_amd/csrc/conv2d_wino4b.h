@@ -360,7 +360,7 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino4b(ConvParams p) {
         const auto& qa = *fresh_args();
         const bool spade = TAIL == W4_TAIL_SPADE ? true : (TAIL == W4_TAIL_ANY ? qa.f.spade_x != nullptr : false);
         const float gain = qa.f.gain, slope = act_slope(qa.f.act, qa.f.alpha);
-        const float cl = qa.f.clamp >= 0.f ? qa.f.clamp : __builtin_inff();
+        const float cl = clamp_bound(qa.f.clamp);
         const bool need_act = slope != 1.f, need_clamp = qa.f.clamp >= 0.f;      // wave-uniform
         const int OHv = qa.OH, OWv = qa.OW, Coutv = qa.Cout;
         const float ngain = qa.f.noise_gain * (spade ? 1.f : gain);
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino4b(ConvParams p) {
             const float g_pos = gain, g_neg = gain * slope;
             if (need_act || need_clamp || gain != 1.f) {
 #pragma unroll
-                for (int e = 0; e < 4; e++) v[e] = __builtin_amdgcn_fmed3f(fmaxf(v[e] * g_pos, v[e] * g_neg), -cl, cl);
+                for (int e = 0; e < 4; e++) v[e] = clamp_tail_med3(fmaxf(v[e] * g_pos, v[e] * g_neg), cl);
             }
             return v;
         };

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fold_head_kernel(const float* 
     if (c < C) mac(c, pA);
 
     if (!colok) return;
-    const float cl = clamp >= 0.f ? clamp : __builtin_inff();
+    const float cl = pg::clamp_bound(clamp);
 #pragma unroll
     for (int o = 0; o < CO; o++) {
         const float bo = bias[n * CO + o];

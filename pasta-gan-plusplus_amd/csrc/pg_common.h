@@ -24,6 +24,14 @@ static inline int launch_status() {
     return e == hipSuccess ? PG_OK : (int)e;
 }
 
+// The clamp of a fused activation tail.  "No clamp" is the bound NaN (clamp_bound): v_max_f32 / v_min_f32 / v_med3_f32 return the operand that is not NaN, so a
+// finite v passes unchanged and a NaN v stays NaN -- with +inf as the bound, max(NaN, -inf) made it -inf.  Under a real clamp a NaN becomes -cl, which is what the
+// reference plugin's select gives (bias_act.cu: `(y > -clamp & y < clamp) ? y : (y >= 0) ? clamp : -clamp`) and what bias_act.hip does.  The instructions are
+// the ones a bound of +inf needs: nothing changes on finite data, nothing is added to a tail.
+__host__ __device__ static inline float clamp_bound(float clamp) { return clamp >= 0.f ? clamp : __builtin_nanf(""); }
+__device__ __forceinline__ float clamp_tail(float v, float cl) { return fminf(fmaxf(v, -cl), cl); }
+__device__ __forceinline__ float clamp_tail_med3(float v, float cl) { return __builtin_amdgcn_fmed3f(v, -cl, cl); }      // (for the tails that clamp with one v_med3_f32)
+
 __host__ __device__ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Compute units of the CURRENT device (256 on MI355X), queried once per device; memory-bound grids are capped at

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void spade_combine16_kernel(const unsigned sho
             const double m = d < 4 ? m0[d & 3] : m1[d & 3], r = d < 4 ? r0[d & 3] : r1[d & 3];
             double v = ((double)xf[d] - m) * r * (1.0 + (double)gf[d]) + (double)bf[d];
             v = (v < 0.0 ? v * slope : v) * (double)gain;
-            v = v > cl ? cl : (v < -cl ? -cl : v);
+            if (clamp >= 0.f) v = (v > -cl && v < cl) ? v : (v >= 0.0 ? cl : -cl);      // the plugin's select: a NaN becomes -clamp, as in every fused tail (pg_common.h)
             o[d] = narrow<T>(v);
         }
         u32x4 ov;

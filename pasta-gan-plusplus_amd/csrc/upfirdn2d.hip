@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tiled(Params p, int tilesX, int
                 if (p.noise) v += p.noise[n * p.noise_bs + (int64_t)oy * p.outW + ox] * p.noise_gain;
                 v += bias;
                 v = (v > 0.f ? v : v * p.slope) * p.act_gain;
-                v = fminf(fmaxf(v, -p.clamp), p.clamp);
+                v = clamp_tail(v, p.clamp);
             }
             yp[(int64_t)oy * p.outW + ox] = (T)v;
             if constexpr (sizeof(T) == 4 && UPX == 1 && UPY == 1 && DNX == 1 && DNY == 1) {
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_blur4(Params p, int tilesX, int
                 for (int c = 0; c < 4; c++) {
                     float w = o[c] + bias;
                     w = (w > 0.f ? w : w * p.slope) * p.act_gain;
-                    o[c] = fminf(fmaxf(w, -p.clamp), p.clamp);
+                    o[c] = clamp_tail(w, p.clamp);
                 }
             }
             *(f32x4f*)(yp + (int64_t)oy * p.outW + ox) = o;
@@ -377,6 +377,10 @@ __global__ __launch_bounds__(256) void upfirdn2d_blur4(Params p, int tilesX, int
         __syncthreads();                                                   // every thread is done with the tile before the next one overwrites it
     }
 }
+
+// Which kernel the last launch of this library went to (pg_upfirdn2d_last_route: the tests assert the route a launch took): 1 the 16-byte blur kernel,
+// 2 a tiled specialisation, 3 a channels-last kernel, 4 the generic kernel, 0 none yet / declined.
+std::atomic<int> g_last_route{0};
 
 // Returns 1 if the 16-byte blur kernel took the call (status in *st).
 inline bool try_blur4(const Params& p, hipStream_t s, int* st) {
@@ -561,7 +565,7 @@ __global__ __launch_bounds__(256, 2) void upfirdn2d_cl(Params p) {
             if (p.has_ep) {
                 v += nz + bias[c];
                 v = (v > 0.f ? v : v * p.slope) * p.act_gain;
-                v = fminf(fmaxf(v, -p.clamp), p.clamp);
+                v = clamp_tail(v, p.clamp);
             }
             out[c] = v;
         }
@@ -650,16 +654,18 @@ int run(const Params& p, hipStream_t s, bool allow_tiled) {
                             p.xs[0] == (int64_t)p.C * p.xs[1] && p.ys[3] == 1 && p.ys[2] == p.outW &&
                             p.ys[1] == (int64_t)p.outH * p.outW && p.ys[0] == (int64_t)p.C * p.outH * p.outW;
     int st = PG_OK;
+    g_last_route = 0;
     if (p.y2) {                                          // the second output exists on the tiled float32 kernel without resampling only
         if constexpr (sizeof(T) == 4) {
-            if (allow_tiled && dense_nchw && !p.has_ep && p.upx == 1 && p.upy == 1 && p.dnx == 1 && p.dny == 1 && try_tiled<T>(p, s, &st)) return st;
+            if (allow_tiled && dense_nchw && !p.has_ep && p.upx == 1 && p.upy == 1 && p.dnx == 1 && p.dny == 1 && try_tiled<T>(p, s, &st)) { g_last_route = 2; return st; }
         }
         return PG_ERR_UNSUPPORTED;
     }
-    if constexpr (sizeof(T) == 4) { if (allow_tiled && dense_nchw && try_blur4(p, s, &st)) return st; }
-    if (allow_tiled && dense_nchw && (!p.has_ep || sizeof(T) == 4) && try_tiled<T>(p, s, &st)) return st;
-    if constexpr (sizeof(T) <= 4) { if (allow_tiled && try_channels_last<T>(p, s, &st)) return st; }
+    if constexpr (sizeof(T) == 4) { if (allow_tiled && dense_nchw && try_blur4(p, s, &st)) { g_last_route = 1; return st; } }
+    if (allow_tiled && dense_nchw && (!p.has_ep || sizeof(T) == 4) && try_tiled<T>(p, s, &st)) { g_last_route = 2; return st; }
+    if constexpr (sizeof(T) <= 4) { if (allow_tiled && try_channels_last<T>(p, s, &st)) { g_last_route = 3; return st; } }
     if (p.has_ep) return PG_ERR_UNSUPPORTED;
+    g_last_route = 4;
     const int64_t total = (int64_t)p.N * p.C * p.outH * p.outW;
     int64_t blocks = (total + 255) / 256;
     if (blocks > max_stream_blocks() * 4) blocks = max_stream_blocks() * 4;
@@ -670,6 +676,7 @@ int run(const Params& p, hipStream_t s, bool allow_tiled) {
 }  // namespace
 
 PG_EXPORT int pg_upfirdn2d_abi_version(void) { return PG_ABI_VERSION; }
+PG_EXPORT int pg_upfirdn2d_last_route(void) { return g_last_route.load(); }
 
 static int upfirdn2d_impl(const void* x, const float* f, void* y, int dtype,
                           int N, int C, int inH, int inW, const int64_t xstride[4],
@@ -693,14 +700,14 @@ static int upfirdn2d_impl(const void* x, const float* f, void* y, int dtype,
     p.flip = flip ? 1 : 0; p.gain = gain;
     p.y2 = y_odd; p.y2H = (outH - 1) / 2; p.y2W = (outW - 1) / 2;
     if (y_odd && (dtype != PG_F32 || p.y2H <= 0 || p.y2W <= 0)) return PG_ERR_UNSUPPORTED;
-    p.has_ep = 0; p.noise = nullptr; p.bias = nullptr; p.noise_bs = 0; p.noise_gain = 0.f; p.slope = 1.f; p.act_gain = 1.f; p.clamp = __builtin_inff();
+    p.has_ep = 0; p.noise = nullptr; p.bias = nullptr; p.noise_bs = 0; p.noise_gain = 0.f; p.slope = 1.f; p.act_gain = 1.f; p.clamp = clamp_bound(-1.f);
     if (ep) {
         if (dtype == PG_F64) return PG_ERR_UNSUPPORTED;
         if (ep->act != 0 && (ep->act < PG_ACT_LINEAR || ep->act > PG_ACT_LRELU)) return PG_ERR_UNSUPPORTED;
         p.has_ep = 1; p.noise = ep->noise; p.noise_bs = ep->noise_batch_stride; p.noise_gain = ep->noise_gain; p.bias = ep->bias;
         p.slope = (ep->act == PG_ACT_RELU) ? 0.f : (ep->act == PG_ACT_LRELU ? ep->alpha : 1.f);
         p.act_gain = ep->act_gain == 0.f ? 1.f : ep->act_gain;
-        p.clamp = ep->clamp >= 0.f ? ep->clamp : __builtin_inff();
+        p.clamp = clamp_bound(ep->clamp);
     }
     hipStream_t s = (hipStream_t)stream;
     switch (dtype) {
