@@ -248,6 +248,9 @@ int pg_conv2d_forward_splitk(const float* x, const float* packed_w, float* y,
  * Every form declines x2 and a pad_x outside [0, 4] (PG_ERR_UNSUPPORTED; use pg_conv2d_forward).  The three F(4x4) forms also decline -- callers then use
  * PG_WINO_F2 -- unless W % 4 == 0, x is 16-byte aligned, there is no input pre-activation stage (in_scale is supported), gain > 0 and an lrelu slope lies
  * in [0, 1] (their tail evaluates the activation as a max), SPADE mode has no in_scale, and stats_partial comes with the plain tail only.
+ * Size limits (PG_ERR_TOO_LARGE): those of pg_conv2d_forward -- one image of x at most 2^31 - 1 bytes, the extent of y (through ystride) at most 2^31 - 1
+ * elements, N * OH * OW at most 2^31 - 1 -- and, for every form, one IMAGE of y (and of residual / spade_x) at most 2^32 - 1 bytes: the tails add 32-bit byte
+ * offsets to a 64-bit per-sample base.  N itself is not bounded: x, y, residual, spade_x and a per-sample noise plane may lie past 2, 4 and 8 GiB.
  */
 enum { PG_WINO_F2 = 1, PG_WINO_F4 = 2, PG_WINO_F4B = 3, PG_WINO_F4X3 = 4 };
 int64_t pg_conv2d_winograd_packed_size(int form, int Cout, int Cin);

@@ -410,8 +410,13 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino(ConvParams p) {
         const int ox0c = ox < q.OW ? ox : q.OW - 1, ox1c = ox + 1 < q.OW ? ox + 1 : q.OW - 1;
         const bool ok0 = row_ok && ox < q.OW, ok1 = row_ok && ox + 1 < q.OW;
         const unsigned cstride_b = (unsigned)q.ys[1] * 4u;
-        const unsigned pix0_b = (unsigned)((int64_t)e_n * q.ys[0] + (int64_t)oyc * q.ys[2] + (int64_t)ox0c * q.ys[3]) * 4u;
-        const unsigned pix1_b = (unsigned)((int64_t)e_n * q.ys[0] + (int64_t)oyc * q.ys[2] + (int64_t)ox1c * q.ys[3]) * 4u;
+        // per-image bases (uniform) + 32-bit byte offsets inside the image (the host checks that one image of y stays below 4 GB)
+        const int64_t img_off = (int64_t)e_n * q.ys[0];
+        float* y_n = q.y + img_off;
+        const float* res_n = q.f.residual ? q.f.residual + img_off : nullptr;
+        const float* spx_n = spade ? q.f.spade_x + img_off : nullptr;
+        const unsigned pix0_b = (unsigned)((int64_t)oyc * q.ys[2] + (int64_t)ox0c * q.ys[3]) * 4u;
+        const unsigned pix1_b = (unsigned)((int64_t)oyc * q.ys[2] + (int64_t)ox1c * q.ys[3]) * 4u;
         const float sg = prow ? -1.f : 1.f;                                   // A^T row: prow 0 -> (+ + +), prow 1 -> (+ - -)
         const bool plain_tail = slope == 1.f && gain == 1.f && q.f.clamp < 0.f;                                // wave-uniform
         f32x2 nz = {0.f, 0.f};
@@ -428,14 +433,14 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino(ConvParams p) {
         };
         auto store2 = [&](unsigned off_b, f32x2 v, bool chan_ok) {
             if (WINO_EXP & 2048) {
-                if (v[0] == 12345.678f) *(f32x2*)((char*)q.y + off_b) = v;
+                if (v[0] == 12345.678f) *(f32x2*)((char*)y_n + off_b) = v;
             } else if (full) {
-                *(f32x2*)((char*)q.y + off_b) = v;
+                *(f32x2*)((char*)y_n + off_b) = v;
             } else if (vec_store) {
-                if (ok0 && chan_ok) *(f32x2*)((char*)q.y + off_b) = v;
+                if (ok0 && chan_ok) *(f32x2*)((char*)y_n + off_b) = v;
             } else {
-                if (ok0 && chan_ok) *(float*)((char*)q.y + off_b) = v[0];
-                if (ok1 && chan_ok) *(float*)((char*)q.y + off_b + (pix1_b - pix0_b)) = v[1];
+                if (ok0 && chan_ok) *(float*)((char*)y_n + off_b) = v[0];
+                if (ok1 && chan_ok) *(float*)((char*)y_n + off_b + (pix1_b - pix0_b)) = v[1];
             }
         };
         const float* exr0 = ex0 + (2 * prow) * 16 * 32 + c_l * 32 + tcol;
@@ -459,11 +464,11 @@ __global__ __launch_bounds__(512, 4) void conv2d_wino(ConvParams p) {
             const int chl = 8 * rnd + c_l;                                   // cout within an M-tile
             f32x2 r0 = {0.f, 0.f}, r1 = {0.f, 0.f};
             if (spade) {
-                r0 = ld2(q.f.spade_x, pix0_b + (unsigned)((e_m0 >> 1) + chl) * cstride_b);
-            } else if (q.f.residual) {
+                r0 = ld2(spx_n, pix0_b + (unsigned)((e_m0 >> 1) + chl) * cstride_b);
+            } else if (res_n) {
                 const int c0 = (full || e_m0 + chl < q.Cout) ? e_m0 + chl : q.Cout - 1, c1 = (full || e_m0 + 32 + chl < q.Cout) ? e_m0 + 32 + chl : q.Cout - 1;
-                r0 = ld2(q.f.residual, pix0_b + (unsigned)c0 * cstride_b);
-                r1 = ld2(q.f.residual, pix0_b + (unsigned)c1 * cstride_b);
+                r0 = ld2(res_n, pix0_b + (unsigned)c0 * cstride_b);
+                r1 = ld2(res_n, pix0_b + (unsigned)c1 * cstride_b);
             }
             __syncthreads();
             if (rnd == 0) {
@@ -530,6 +535,10 @@ int launch_wino_xf(const ConvParams& p0, hipStream_t s) {
     const int cin_loop = ((p.Cin + W_KC - 1) / W_KC) * W_KC;
     const size_t lds = ((size_t)2 * W_BUFS + 2 * W_EXCH + 2 * cin_loop + 256 + (VEC ? 6 * 256 : 0)) * sizeof(float);
     if ((int64_t)16 * cin_loop * p.CoutP * 4 > 0x7fffffffLL) return PG_ERR_TOO_LARGE;      // the U stream uses 32-bit byte offsets
+    {   // the tail addresses one image of y / residual / spade_x with 32-bit byte offsets (the sample base is a 64-bit pointer)
+        const int64_t ext = 1 + (int64_t)(p.f.spade_x ? p.Cout / 2 - 1 : p.Cout - 1) * p.ys[1] + (int64_t)(p.OH - 1) * p.ys[2] + (int64_t)(p.OW - 1) * p.ys[3];
+        if (ext * 4 > 0xffffffffLL) return PG_ERR_TOO_LARGE;
+    }
     if (lds > 160 * 1024) return PG_ERR_UNSUPPORTED;
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 2) per_cu = 2;                             // 128 VGPRs x 8 waves per workgroup

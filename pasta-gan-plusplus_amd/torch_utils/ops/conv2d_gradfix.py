@@ -103,6 +103,31 @@ def _epilogue_cfg(ep):
     return (act, alpha, gain, clamp)
 
 
+ATEN_MAX_ELEMENTS = 1 << 30      # per aten call: input and output of one call stay below 2^31 elements with a factor of two to spare
+
+
+def _aten_batched(fn, input, grow=1, **kw):
+    """`fn(input, **kw)` (an aten convolution) in batch chunks whose input and output stay below ATEN_MAX_ELEMENTS.  aten's GPU convolution indexes a
+    batch with 32 bits: on an output past 2^31 elements the samples behind that index came back as copies of the first ones (measured: 16 -> 16 channels,
+    1x1, 64 x 64, N = 32802 -- sample 32768 onward), silently.  This is the route a launch takes that the native kernels decline as PG_ERR_TOO_LARGE, so it must
+    hold exactly there.  Small tensors take one call, as before (`grow`: output pixels per input pixel, for the estimate that decides it)."""
+    n = int(input.shape[0]) if input.ndim == 4 else 1
+    wide = max(int(d) for d in kw['weight'].shape[:2]) * int(kw.get('groups', 1))          # no fewer than the channels of either side
+    if not input.is_cuda or n <= 1 or input.numel() // max(1, int(input.shape[1])) * wide * grow <= ATEN_MAX_ELEMENTS // 2:
+        return fn(input=input, **kw)
+    with torch.no_grad():
+        one = fn(input=input[:1].detach(), **{k: (v.detach() if torch.is_tensor(v) else v) for k, v in kw.items()})          # (for the output's shape)
+    step = max(1, ATEN_MAX_ELEMENTS // max(input[0].numel(), one[0].numel()))
+    if step >= n:
+        return fn(input=input, **kw)
+    if torch.is_grad_enabled() and (input.requires_grad or any(torch.is_tensor(v) and v.requires_grad for v in kw.values())):
+        return torch.cat([fn(input=input[i:i + step], **kw) for i in range(0, n, step)])
+    out = torch.empty([n, *one.shape[1:]], dtype=one.dtype, device=one.device)
+    for i in range(0, n, step):
+        out[i:i + step] = fn(input=input[i:i + step], **kw)
+    return out
+
+
 def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, _epilogue=None):
     """`_epilogue` (private): dict(act, alpha, gain, clamp) -- `bias_act(conv2d(...) , act=...)` of the caller (the bias is this call's
     `bias`), run in the native convolution's epilogue with the derivative taken from the saved output, or as the separate op where the
@@ -129,7 +154,7 @@ def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, 
             pass
     if weight.dtype != input.dtype:
         weight = weight.to(input.dtype)
-    return tail(torch.nn.functional.conv2d(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups))
+    return tail(_aten_batched(torch.nn.functional.conv2d, input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups))
 
 
 def _phases_supported(mod, kh, kw, s):
@@ -153,8 +178,8 @@ def conv_transpose2d(input, weight, bias=None, stride=1, padding=0, output_paddi
             pass
     if weight.dtype != input.dtype:
         weight = weight.to(input.dtype)
-    return torch.nn.functional.conv_transpose2d(input=input, weight=weight, bias=bias, stride=stride, padding=padding,
-                                                output_padding=output_padding, groups=groups, dilation=dilation)
+    return _aten_batched(torch.nn.functional.conv_transpose2d, input, grow=2 * max(_pair(stride)) ** 2, weight=weight, bias=bias, stride=stride, padding=padding,
+                         output_padding=output_padding, groups=groups, dilation=dilation)
 
 
 UP2_TRANSPOSED = os.environ.get('PG_UP2_TRANSPOSED', '1') != '0'      # A/B: 0 = the transposed 3x3 stride-2 convolution as four phase launches

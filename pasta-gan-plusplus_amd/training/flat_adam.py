@@ -16,11 +16,19 @@ from torch_utils.ops import _native as nat
 from torch_utils.ops import conv2d_mfma
 
 
+MAX_FLAT_ELEMENTS = (1 << 31) - 1      # adam_flat_kernel (csrc/optim.hip) and the int32 chunk table address the flat buffers with 32-bit element offsets
+
+
+def check_flat_size(numel):
+    assert int(numel) <= MAX_FLAT_ELEMENTS, f'FlatAdam: a flat buffer of {int(numel)} elements is past the 32-bit offsets of pg_adam_flat_step ({MAX_FLAT_ELEMENTS})'
+
+
 class FlatAdam:
     def __init__(self, bucket, lr, betas, eps, nan=0.0, posinf=1e5, neginf=-1e5, share_params_with=None):
         """`share_params_with`: another FlatAdam over the SAME bucket whose flat parameter buffer this one steps too, with moments and step counts of its
         own -- the reference lists D_parsing twice in its phase table (training_loop_fullbody.py:470-471), i.e. two optimizers over one module."""
         assert bucket.flat.is_cuda, 'FlatAdam is the GPU path; CPU tensors keep torch.optim.Adam'
+        check_flat_size(bucket.flat.numel())
         self.bucket, self.lr, self.betas, self.eps = bucket, float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.nan, self.posinf, self.neginf = float(nan), float(posinf), float(neginf)
         lib = conv2d_mfma._init().lib
