@@ -18,6 +18,7 @@
  *   vgg_loss_plugin.so      pg_maxpool2x2, pg_maxpool2x2_backward, pg_l1_pair_blocks, pg_l1_pair_sum, pg_l1_pair_grad
  *   image_metrics_plugin.so pg_image_pair_metrics_workspace, pg_image_pair_metrics_u8
  *   region_metrics_plugin.so pg_region_pair_metrics_workspace, pg_region_pair_metrics_u8, pg_label_confusion_u8
+ *   contextual_plugin.so    pg_cx_padded_channels, pg_cx_prepare, pg_cx_prepare_backward, pg_cx_forward, pg_cx_backward
  * plus pg_<plugin>_abi_version() in each.  They are what the reference's L1
  * Python ops bind in place of its pybind plugins (see INTEGRATION.md for the
  * ctypes stub a maintainer adds to the reference tree).
@@ -938,6 +939,37 @@ int pg_region_pair_metrics_u8(const pg_region_pair* jobs_host, const pg_region_p
 int pg_label_confusion_u8(const pg_label_pair* jobs_host, const pg_label_pair* jobs_device, int npairs, const unsigned char* pred_lut,
                           const unsigned char* target_lut, int classes, int64_t* out, void* stream);
 int pg_region_metrics_abi_version(void);
+
+/* contextual_plugin.so -- the contextual loss (torch_utils/ops/contextual_ops.py, training/contextual_loss.py).  float32.  x = `samples` = G * n
+ * feature maps [channels, positions] (G <= PG_CX_MAX_GROUPS groups of n stacked on the batch axis), y = n of them; sample s of x meets sample s % n
+ * of y.  Per sample, with mu_p = mean_c y[c][p], xn_p = (x_p - mu_p) / (|x_p - mu_p| + 2.220446049250313e-16), yn likewise, d_ij = 1 - xn_i . yn_j:
+ *   m_i = min_j d_ij at jmin_i (lowest j on ties), e_i = m_i + 1e-3, w_ij = exp((1 - d_ij / e_i) / h), S_i = sum_j w_ij,
+ *   a_i = max_j w_ij / S_i (at jmin_i: w falls with d), CX = mean_i a_i, loss = -log CX.
+ * No positions x positions element is written to memory: the products are streamed on the float32 matrix instruction.  No atomics (bit-identical
+ * run to run), nothing read to the host, no allocation; every element of every output is written.
+ * pg_cx_padded_channels: Cp = channels rounded up to 32 (0 for channels < 1).
+ * pg_cx_prepare: xn [samples, positions, Cp], yn [n, positions, Cp] (position-major, padding zero, 16-byte aligned) and rx [samples, positions] =
+ *   |x_p - mu_p|, from dense NCHW x and y of any alignment.  One launch.
+ * pg_cx_prepare_backward: dx (dense NCHW) from dxn [samples, positions, Cp]: dx_p = (dxn_p - xn_p (xn_p . dxn_p) (r + eps) / r) / (r + eps), r = rx_p;
+ *   a zero row where r == 0.
+ * pg_cx_forward: the row statistics row_min = m, row_argmin = jmin, row_others = S' = sum_{j != jmin} w_ij, row_wd = T' = sum_j w_ij (d_ij - m_i) and
+ *   row_a = a [samples, positions], and cx, loss [samples].  Two launches.
+ * pg_cx_backward: dxn [samples, positions, Cp] = (g a / (h e)) (yn_jmin - V) - (g a (m - D) / (h e^2)) yn_jmin per row, g = -gout[s] / (positions
+ *   cx[s]), V_i = sum_j (w_ij / S_i) yn_j, D_i = sum_j w_ij d_ij / S_i, both differences formed from S', T' and U' = sum_{j != jmin} w_ij yn_j without
+ *   a cancellation; `gout` = `samples` device floats.  One launch.
+ * PG_ERR_INVALID_ARG: NULL pointer, non-positive size, samples % n != 0, h <= 0; PG_ERR_UNSUPPORTED: more than PG_CX_MAX_GROUPS groups, a
+ * position-major operand that is not 16-byte aligned; PG_ERR_TOO_LARGE: positions > 2^31 - 129, samples + n > 65535, an extent past 2^60. */
+#define PG_CX_MAX_GROUPS 8
+#define PG_CX_CHANNEL_PAD 32
+int pg_cx_padded_channels(int channels);
+int pg_cx_prepare(const float* x, const float* y, float* xn, float* yn, float* rx, int samples, int n, int channels, int64_t positions, void* stream);
+int pg_cx_prepare_backward(const float* dxn, const float* xn, const float* rx, float* dx, int samples, int channels, int64_t positions, void* stream);
+int pg_cx_forward(const float* xn, const float* yn, float* row_min, int* row_argmin, float* row_others, float* row_wd, float* row_a, float* cx,
+                  float* loss, int samples, int n, int channels, int64_t positions, double h, void* stream);
+int pg_cx_backward(const float* xn, const float* yn, const float* row_min, const int* row_argmin, const float* row_others, const float* row_wd,
+                   const float* row_a, const float* cx, const float* gout, float* dxn, int samples, int n, int channels, int64_t positions, double h,
+                   void* stream);
+int pg_contextual_abi_version(void);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@ PLUGIN_SOURCES = {
     'vgg_loss_plugin': ['vgg_loss.hip'],
     'image_metrics_plugin': ['image_metrics.hip'],
     'region_metrics_plugin': ['region_metrics.hip'],
+    'contextual_plugin': ['contextual.hip'],
     'conv2d_plugin': ['conv2d.hip', 'conv2d_inst_k3s1.hip', 'conv2d_inst_k1s1.hip', 'conv2d_inst_k2x2.hip', 'conv2d_inst_k2x1.hip',
                       'conv2d_inst_k1x2.hip', 'conv2d_inst_k7s1.hip', 'conv2d_inst_k3s2.hip', 'conv2d_inst_k1s2.hip', 'conv2d_inst_wino.hip', 'conv2d_inst_wino4.hip', 'conv2d_inst_wino4s.hip', 'conv2d_inst_wino4t.hip', 'conv2d_inst_wino4x.hip', 'conv2d_inst_wino4xs.hip', 'conv2d_inst_wino4xt.hip', 'conv2d_inst_wino4b.hip', 'conv2d_inst_wino4bs.hip', 'conv2d_inst_up2.hip', 'conv2d_inst_stem7.hip', 'conv2d_inst_s2x3.hip', 'conv2d_inst_s1x1.hip',
                       'conv2d_wgrad.hip', 'conv2d16.hip', 'conv2d16_inst_k3s1.hip', 'conv2d16_inst_k3s1b.hip', 'conv2d16_inst_k1s1.hip', 'conv2d16_inst_k2x2.hip', 'conv2d16_inst_k2x1.hip',

@@ -5,7 +5,10 @@ on the parsing head, and lazy R1 on both discriminators.
 
 The VGG19 perceptual term (:178-193, :336-386) is on with ``vgg_weight > 0`` and a ``training.vgg_loss.VGGLoss`` passed as ``vgg``: its
 weights come from a checkpoint that is not shipped (``./checkpoints/vgg19-dcbb9e9d.pth`` in the reference), so without one the term is
-refused.  Not restated: the contextual term (:487-618), which the reference never calls (``train.sh`` runs with contextual_weight 0).
+refused.  The contextual term (:481-618) is on with ``contextual_weight > 0`` and a ``training.contextual_loss.ContextualLoss`` passed as
+``contextual``; its trunk's checkpoint (``./checkpoints/vgg19_conv.pth`` in the reference) is not shipped either, so without a module the term
+is refused.  The reference constructs that term's classes and never calls them (``train.sh`` runs with contextual_weight 0): the classes are
+restated and pinned, the way they enter Gmain -- like the VGG term, on both generated images -- is this package's choice.
 Path-length regularisation is commented out in the reference (:200-221), so a ``Greg`` phase only runs the style encoder.
 
 Gradient synchronisation is NOT done here (the reference toggles DDP's hooks through ``ddp_sync``, letting only the
@@ -25,9 +28,11 @@ _G_PARTS = ('G_mapping', 'G_synthesis', 'G_const_encoding', 'G_style_encoding')
 class StyleGAN2Loss:
     def __init__(self, device, G_mapping, G_synthesis, G_const_encoding, G_style_encoding, D, D_parsing, augment_pipe=None,
                  style_mixing_prob=0.9, r1_gamma=10, pl_batch_shrink=2, pl_decay=0.01, pl_weight=0, l1_weight=50, vgg_weight=0,
-                 contextual_weight=0, mask_weight=1.0, report=None, vgg=None):
-        if contextual_weight:
-            raise NotImplementedError('the contextual term is not restated (the reference never calls it)')
+                 contextual_weight=0, mask_weight=1.0, report=None, vgg=None, contextual=None):
+        if contextual_weight and contextual is None:
+            raise NotImplementedError('contextual_weight > 0 needs a checkpoint (vgg19_conv.pth is not shipped): pass '
+                                      'contextual=ContextualLoss(VGG19ConvFeatures(load_vgg19_conv(path))) (training/contextual_loss.py)')
+        self.contextual_weight, self.contextual = contextual_weight, (contextual if contextual_weight else None)
         if vgg_weight and vgg is None:
             raise NotImplementedError('vgg_weight > 0 needs a checkpoint: pass vgg=VGGLoss(VGG19Features(load_vgg19(path))) (training/vgg_loss.py)')
         self.vgg_weight, self.vgg = vgg_weight, (vgg if vgg_weight else None)
@@ -111,6 +116,11 @@ class StyleGAN2Loss:
                 loss_G = loss_G + (vgg + vgg_fine) / 2
                 self.report('Loss/G/vgg', vgg)
                 self.report('Loss/G/vgg_finetune', vgg_fine)
+            if self.contextual is not None:                          # the real image's features are computed once for both
+                ctx, ctx_fine = (self.contextual([gen_img, gen_fine], real_img) * self.contextual_weight).unbind(0)
+                loss_G = loss_G + (ctx + ctx_fine) / 2
+                self.report('Loss/G/contextual', ctx)
+                self.report('Loss/G/contextual_finetune', ctx_fine)
             self.report('Loss/G/loss', adv)
             self.report('Loss/G/L1', l1)
             self.report('Loss/G/mask_loss', ce)

@@ -98,3 +98,20 @@ def vgg19_state_dict(classifier=False):
             sd[f'classifier.{idx}.weight'] = torch.zeros([]).expand(cout, cin)
             sd[f'classifier.{idx}.bias'] = torch.zeros([]).expand(cout)
     return sd
+
+
+# the reference's VGG19_feature_color_torchversion (training/loss_fullbody.py:494-519): attribute name -> (Cin, Cout) of its sixteen convolutions
+VGG19_CONV_NAMES = {'conv1_1': (3, 64), 'conv1_2': (64, 64), 'conv2_1': (64, 128), 'conv2_2': (128, 128), 'conv3_1': (128, 256),
+                    'conv3_2': (256, 256), 'conv3_3': (256, 256), 'conv3_4': (256, 256), 'conv4_1': (256, 512), 'conv4_2': (512, 512),
+                    'conv4_3': (512, 512), 'conv4_4': (512, 512), 'conv5_1': (512, 512), 'conv5_2': (512, 512), 'conv5_3': (512, 512),
+                    'conv5_4': (512, 512)}
+
+
+def vgg19_conv_state_dict():
+    """A state dict under the key names of the reference's ``vgg19_conv.pth`` (``conv1_1.weight ... conv5_4.bias``; the pretrained file is not
+    available offline), with ``vgg19_state_dict``'s He weights and small biases under name-keyed values of their own."""
+    sd = {}
+    for name, (cin, cout) in VGG19_CONV_NAMES.items():
+        sd[f'{name}.weight'] = det_tensor(f'vgg19_conv.{name}.weight', [cout, cin, 3, 3], scale=(2.0 / (9 * cin)) ** 0.5)
+        sd[f'{name}.bias'] = det_tensor(f'vgg19_conv.{name}.bias', [cout], scale=0.05)
+    return sd

@@ -7,8 +7,9 @@ module builds the networks, runs the two until `kimg`, prints the reference's st
 Snapshots are plain ``torch.save`` dicts of ``state_dict``s under the reference's parameter names -- ``G``, ``D``, ``D_parsing``, ``G_ema``,
 ``augment_p``, ``cur_nimg`` -- which ``--resume`` reads back; ``--resume`` also reads a reference snapshot (.pkl) through ``checkpoint.load_into``
 (nothing in it is executed).  The VGG19 perceptual term (``vgg_weight`` > 0) needs ``vgg_ckpt``, a torchvision-format ``vgg19`` state dict
-(training/vgg_loss.py); its tensors are buffers of the loss, in no snapshot.  Writing the reference's own pickle format is out of scope (its
-pickles embed module source), as are the contextual term, the reference's detector-based metrics (FID, KID, PR, PPL, IS), zip datasets and
+(training/vgg_loss.py); its tensors are buffers of the loss, in no snapshot.  The contextual term (``contextual_weight`` > 0) likewise needs
+``contextual_ckpt``, a state dict under the reference's ``vgg19_conv.pth`` key names (training/contextual_loss.py).  Writing the reference's own
+pickle format is out of scope (its pickles embed module source), as are the reference's detector-based metrics (FID, KID, PR, PPL, IS), zip datasets and
 tensorboard.  ``metrics`` (``--metrics l1,psnr,ssim``) is opt-in: on image-snapshot ticks the reconstruction error of the grid's diagonal cells goes
 into ``stats.jsonl`` as ``Metric/recon_*`` (training/metrics.py); ``--metric-regions`` restricts it to label regions as well, and the name
 ``parsing`` scores the parsing head (``Metric/parsing_*``)."""
@@ -99,12 +100,12 @@ def check_augment_options(aug, p, augpipe):
 
 def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, mask_weight=1.0, vgg_weight=0, contextual_weight=0, aug='ada', target=0.6,
                   seed=0, workers=3, kimg=25000, tick=4, snap=50, resume=None, device='cuda', width=None, dataset_kwargs=None, on_start=None, image_snap=None,
-                  vgg_ckpt=None, metrics=None, augpipe='bgc', p=None, metric_regions=None):
+                  vgg_ckpt=None, metrics=None, augpipe='bgc', p=None, metric_regions=None, contextual_ckpt=None):
     """Train on the dataset directory `data` for `kimg` thousand images (one process, one GPU: `batch` = `batch_gpu` x accumulation rounds).
     Returns the `TrainingStep`.  `width` narrows the networks (tests); `on_start(G, D, D_parsing, G_ema)` is called after `resume` was applied.
     `snap` drives both kinds of snapshot, as in the reference; `image_snap` overrides the interval of the image grids (0: none).
     `vgg_weight` > 0 turns the VGG19 perceptual term on and needs `vgg_ckpt` (no default path): NotImplementedError without one, FileNotFoundError for
-    a path that does not exist, both before any network is built.  `metrics`: None, or names out of 'l1', 'psnr', 'ssim' -- each image-snapshot tick
+    a path that does not exist, both before any network is built; `contextual_weight` > 0 and `contextual_ckpt` likewise.  `metrics`: None, or names out of 'l1', 'psnr', 'ssim' -- each image-snapshot tick
     then adds ``Metric/recon_<name>`` (training/metrics.py) to its ``stats.jsonl`` line and prints them after the status line -- and 'parsing':
     ``Metric/parsing_acc`` / ``Metric/parsing_miou`` of the grid's predicted parsing.  `metric_regions`: None, or names out of ``metrics.REGIONS`` --
     ``Metric/recon_<name>_<region>`` for each selected l1 / psnr / ssim (ValueError, before anything is built, when none of the three is selected).
@@ -114,6 +115,10 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
         raise NotImplementedError('vgg_weight > 0 needs --vgg_ckpt: a torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth is not shipped)')
     if vgg_weight and not os.path.isfile(vgg_ckpt):
         raise FileNotFoundError(f'--vgg_ckpt "{vgg_ckpt}" does not exist')
+    if contextual_weight and contextual_ckpt is None:
+        raise NotImplementedError('contextual_weight > 0 needs --contextual_ckpt: a state dict under the key names of vgg19_conv.pth (which is not shipped)')
+    if contextual_weight and not os.path.isfile(contextual_ckpt):
+        raise FileNotFoundError(f'--contextual_ckpt "{contextual_ckpt}" does not exist')
     metrics_mod = None
     if metrics:
         from . import metrics as metrics_mod
@@ -148,8 +153,12 @@ def training_loop(run_dir, data, batch=32, batch_gpu=4, gamma=10, l1_weight=50, 
     if vgg_weight:
         from . import vgg_loss
         vgg = vgg_loss.VGGLoss(vgg_loss.VGG19Features(vgg_loss.load_vgg19(vgg_ckpt))).to(dev)
+    contextual = None
+    if contextual_weight:
+        from . import contextual_loss as cx
+        contextual = cx.ContextualLoss(cx.VGG19ConvFeatures(cx.load_vgg19_conv(contextual_ckpt))).to(dev)
     loss = StyleGAN2Loss(device=dev, **parts, D=D, D_parsing=D_parsing, style_mixing_prob=0.9, r1_gamma=gamma, l1_weight=l1_weight, vgg_weight=vgg_weight,
-                         vgg=vgg, contextual_weight=contextual_weight, mask_weight=mask_weight, report=report)
+                         vgg=vgg, contextual_weight=contextual_weight, contextual=contextual, mask_weight=mask_weight, report=report)
     pipe = augment.AugmentPipe(**augment.AUGPIPE_SPECS[augpipe]).to(dev).set_native_late(dev.type == 'cuda') if aug != 'noaug' else None
     if aug == 'fixed':
         augment_p = p
@@ -224,7 +233,8 @@ def parse_args(argv=None):
     p.add_argument('--mask_weight', type=float, default=1.0)
     p.add_argument('--vgg_weight', type=float, default=0, help='weight of the VGG19 perceptual term (the reference\'s train.sh: 20); > 0 needs --vgg_ckpt')
     p.add_argument('--vgg_ckpt', default=None, help='torchvision-format vgg19 state dict (vgg19-dcbb9e9d.pth); no default path')
-    p.add_argument('--contextual_weight', type=float, default=0, help='only 0 is supported')
+    p.add_argument('--contextual_weight', type=float, default=0, help='weight of the contextual term (the reference\'s train.sh: 0); > 0 needs --contextual_ckpt')
+    p.add_argument('--contextual_ckpt', default=None, help='state dict under the key names of the reference\'s vgg19_conv.pth; no default path')
     p.add_argument('--aug', choices=['ada', 'noaug', 'fixed'], default='ada', help="augmentation mode; 'fixed' needs --p")
     p.add_argument('--p', type=float, default=None, help='augmentation probability for --aug=fixed')
     p.add_argument('--target', type=float, default=0.6, help='ADA target')
@@ -268,5 +278,5 @@ def main(argv=None):
         raise SystemExit(str(e))
     return training_loop(a.outdir, a.data, batch=a.batch, batch_gpu=a.batch_gpu, gamma=a.gamma, l1_weight=a.l1_weight, mask_weight=a.mask_weight,
                          vgg_weight=a.vgg_weight, contextual_weight=a.contextual_weight, aug=a.aug, target=a.target, seed=a.seed, workers=a.workers,
-                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt, metrics=metrics,
+                         kimg=a.kimg, tick=a.tick, snap=a.snap, resume=a.resume, device=a.device, image_snap=a.image_snap, vgg_ckpt=a.vgg_ckpt, contextual_ckpt=a.contextual_ckpt, metrics=metrics,
                          augpipe=a.augpipe, p=a.p, metric_regions=regions)
